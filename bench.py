@@ -6,6 +6,11 @@ seq 4096, ZeRO-1 AdamW — the BASELINE.json headline metric
 Single GPU:     python bench.py --steps 8 --warmup 3
 N GPUs (driver): python -m torch.distributed.run --nnodes=1 --nproc-per-node N
                  --master-addr 127.0.0.1 bench.py --gpus N --steps K --warmup W
+
+--dump-outputs DIR writes the last timed step's loss and a fixed sample of
+the updated weights as .npy files; inputs and initial weights are seeded, so
+the same arguments give the same inputs in every run.  --full is reserved
+for measurements beyond the headline figure.
 """
 
 import argparse
@@ -35,7 +40,37 @@ def parse_args():
                    help="override layer count (debug only; overridden runs "
                         "are marked invalid in the output)")
     p.add_argument("--microbatch", type=int, default=8)
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="after the timed steps, write what the last timed "
+                        "step produced (loss, a seeded sample of the updated "
+                        "weights) as DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run the measurements beyond the headline "
+                        "figure (none at present: the plain run is the "
+                        "whole benchmark)")
     return p.parse_args()
+
+
+def dump_outputs(out_dir, loss, params, suffix="", per_param=4096):
+    """Write the last timed step's results as float32 .npy files: the loss
+    the step returned and the weights it left behind.  The weights are a
+    fixed sample - the same ``per_param`` seeded positions of every
+    parameter tensor in every run - so two builds compare element for
+    element (a few MB for Llama-2-7B)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, f"loss{suffix}.npy"),
+            loss.detach().float().cpu().numpy().reshape(1))
+    gen = torch.Generator().manual_seed(2024)
+    sample = []
+    for p in params:
+        flat = p.detach().reshape(-1)
+        idx = torch.randint(0, flat.numel(), (min(per_param, flat.numel()),),
+                            generator=gen)
+        sample.append(flat[idx.to(flat.device)].float().cpu())
+    np.save(os.path.join(out_dir, f"params_sample{suffix}.npy"),
+            torch.cat(sample).numpy())
 
 
 def main():
@@ -187,6 +222,11 @@ def main():
     t = torch.tensor([elapsed], dtype=torch.float64, device=device)
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = t.item()
+
+    if args.dump_outputs:
+        # each rank holds its own shard of the weights
+        dump_outputs(args.dump_outputs, loss, params,
+                     suffix="" if world == 1 else f"_rank{rank}")
 
     tokens = B * S * args.steps
     ms_per_step = elapsed / args.steps * 1000.0

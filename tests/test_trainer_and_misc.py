@@ -350,6 +350,48 @@ def test_bench_tp4_cpu_smoke():
     assert r["value"] > 0
 
 
+def test_bench_dump_outputs(tmp_path):
+    """bench.py --dump-outputs: a plain (and --full) single-process run
+    writes the last timed step's loss and the weight sample as finite
+    float32 .npy files, the dumped loss is the one in the result line, and
+    two runs with the same arguments sample the same positions."""
+    import json
+    import subprocess
+    import sys
+
+    import numpy as np
+
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumps = []
+    for name, extra in (("a", []), ("b", ["--full"])):
+        out_dir = tmp_path / name
+        cmd = [sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1",
+               "--steps", "2", "--warmup", "1", "--model", "tiny",
+               "--seq", "64", "--batch", "2", "--microbatch", "1",
+               "--dump-outputs", str(out_dir)] + extra
+        env = dict(os.environ, MASTER_PORT=str(_free_port()))
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=420,
+                             cwd=repo, env=env)
+        assert out.returncode == 0, out.stderr[-2000:]
+        r = json.loads([l for l in out.stdout.splitlines()
+                        if l.startswith("{")][-1])
+        assert r["steps"] == 2 and r["ms_per_step"] > 0
+        loss = np.load(out_dir / "loss.npy")
+        sample = np.load(out_dir / "params_sample.npy")
+        assert loss.dtype == np.float32 and loss.shape == (1,)
+        assert sample.dtype == np.float32 and sample.size > 1000
+        assert np.isfinite(loss).all() and np.isfinite(sample).all()
+        assert abs(float(loss[0]) - r["config"]["loss"]) < 1e-6
+        dumps.append((loss, sample))
+    assert dumps[0][1].shape == dumps[1][1].shape
+    # same seeded inputs and sample positions: the bf16 weights of two runs
+    # agree to one bf16 ulp (2^-7 relative; reduction order on a GPU may
+    # differ) plus a few steps' update (lr 1.5e-4)
+    np.testing.assert_allclose(dumps[0][0], dumps[1][0], rtol=1e-3)
+    np.testing.assert_allclose(dumps[0][1], dumps[1][1], rtol=2 ** -7,
+                               atol=1e-3)
+
+
 def _dp_loader_worker(rank, world):
     """create_dp_dataloader: TP ranks share batches; DP shards them."""
     from neuronx_distributed_amd.parallel import parallel_state as ps
