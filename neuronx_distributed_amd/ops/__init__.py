@@ -479,8 +479,16 @@ class _FlashAttnFn(torch.autograd.Function):
         dq = _fa_alloc_like(q)
         # dk/dv are written bf16 PER Q-HEAD (B,Hq,S,D); GQA replicas are
         # reduced here (each replica covers distinct Q heads -> SUM)
-        dk_pq = torch.empty(B, Hq, S, D, dtype=q.dtype, device=q.device)
-        dv_pq = torch.empty(B, Hq, S, D, dtype=q.dtype, device=q.device)
+        if Hq == Hkv:
+            # no reduction: write dk/dv straight in k's/v's layout, so a
+            # BSHD-view k/v gets BSHD grads and the consumers' .contiguous()
+            # stays a no-op (the kernels take the strides)
+            dk_pq = _fa_alloc_like(k)
+            dv_pq = _fa_alloc_like(v)
+        else:
+            # the .view(B, Hkv, rep, S, D) reduction needs contiguous BHSD
+            dk_pq = torch.empty(B, Hq, S, D, dtype=q.dtype, device=q.device)
+            dv_pq = torch.empty(B, Hq, S, D, dtype=q.dtype, device=q.device)
         lib.flash_attn_bwd_strided(
             _ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(dout),
             _ptr(lse), _ptr(delta), _ptr(dq), _ptr(dk_pq), _ptr(dv_pq),

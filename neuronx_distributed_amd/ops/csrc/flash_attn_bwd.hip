@@ -13,6 +13,12 @@
 // No atomics anywhere: every output region is written by exactly one
 // workgroup.
 //
+// Staging: every tile (Q, dO in dkdv; K, V in dq) is stored in LDS ONCE,
+// in the dual-use image of mfma.h, and read both row-wise (ds_read_b128)
+// and transposed (ds_read_b64_tr_b16).  Both kernels double-buffer the
+// staged tiles.  LDS budget: dkdv 2 x 33,280 B staging + 32,768 B exchange
+// = 99,328 B (1 WG/CU); dq 2 x 32,768 B = 65,536 B (2 WG/CU).
+//
 // Orientation trick shared with the forward kernel: all mfmas keep the
 // softmax-normalized index (q) on the lane axis (col = l&31) so lse/delta
 // are per-lane scalars; operands that need the other orientation go
@@ -20,11 +26,6 @@
 
 #include "common.h"
 #include "mfma.h"
-
-// transposed tiles use a PADDED pitch instead of a swizzle: 80-byte rows
-// (40 bf16) are 16B-aligned and put row d on bank 4*(5d mod 16) -> all
-// distinct within a b128 lane group (5 coprime to 16) -> conflict-free.
-#define TR_PITCH 40
 
 #define FA_D 128
 #define LOG2E 1.4426950408889634f
@@ -66,149 +67,63 @@ fa_bwd_delta_kernel(const short* __restrict__ dout,
 // shared helpers for the two main kernels
 // ---------------------------------------------------------------------------
 
-// stage a 32x128 bf16 tile row-major (XOR-swizzled) + transposed [128][32]
-// copy, using all 256 threads (2x16B pieces each for row-major; scatter b16
-// for the transpose).  row stride row-major: 256 B; transposed: 64 B.
+// Stage a 64x128 bf16 tile ONCE, in the dual-use image of mfma.h (256-byte
+// rows, chunk XOR of img_off): the same copy feeds the ds_read_b128 row
+// reads (S^T / dP^T A fragments) and the ds_read_b64_tr_b16 transposed
+// reads (B fragments of the dV/dK/dQ mfmas).  Thread t owns NR consecutive
+// rows at 16-byte chunk t&15 (NR = 64*16 / blockDim.x), i.e. NR coalesced
+// b128 global loads and NR ds_write_b128.  Rows past the end of the
+// sequence are CLAMPED, never skipped: every image row always holds data,
+// so the transposed reads run with all lanes active (pad, don't mask).
+#define TILE64_B (64 * IMG_ROW_B)   // 16384 B
 
-struct StageRegs { uint4v v0, v1; };
+template <int NR>
+struct StageRegs { uint4v v[NR]; };
 
-__device__ __forceinline__ StageRegs load_tile32(const short* __restrict__ src,
-                                                 long src_row0,
-                                                 long src_stride,
-                                                 int rows_valid) {
-  int rp = (threadIdx.x & 255) >> 4;
-  int c16 = threadIdx.x & 15;
-  int r0 = 2 * rp, r1 = 2 * rp + 1;
-  int rr0 = r0 < rows_valid ? r0 : (rows_valid > 0 ? rows_valid - 1 : 0);
-  int rr1 = r1 < rows_valid ? r1 : (rows_valid > 0 ? rows_valid - 1 : 0);
-  StageRegs r;
-  r.v0 = *(const uint4v*)(src + (src_row0 + rr0) * src_stride + c16 * 8);
-  r.v1 = *(const uint4v*)(src + (src_row0 + rr1) * src_stride + c16 * 8);
+template <int NR>
+__device__ __forceinline__ StageRegs<NR> load_tile64(
+    const short* __restrict__ src, long src_row0, long src_stride,
+    int rows_valid) {
+  const int rp = threadIdx.x >> 4;
+  const int c16 = threadIdx.x & 15;
+  const int last = rows_valid > 0 ? rows_valid - 1 : 0;
+  StageRegs<NR> r;
+#pragma unroll
+  for (int i = 0; i < NR; ++i) {
+    int row = NR * rp + i;
+    int rr = row < rows_valid ? row : last;
+    r.v[i] = *(const uint4v*)(src + (src_row0 + rr) * src_stride + c16 * 8);
+  }
   return r;
 }
 
-__device__ __forceinline__ void write_tile32(StageRegs r, char* lds_rm,
-                                             char* lds_tr) {
-  if (blockDim.x > 256 && threadIdx.x >= 256) return;
-  int rp = threadIdx.x >> 4;
-  int c16 = threadIdx.x & 15;
-  int r0 = 2 * rp, r1 = 2 * rp + 1;
-  *(uint4v*)(lds_rm + r0 * (FA_D * 2) + swz16(r0, c16 * 16)) = r.v0;
-  *(uint4v*)(lds_rm + r1 * (FA_D * 2) + swz16(r1, c16 * 16)) = r.v1;
-  union { uint4v u; short s[8]; } a, b;
-  a.u = r.v0; b.u = r.v1;
+template <int NR>
+__device__ __forceinline__ void write_tile64(StageRegs<NR> r, char* img) {
+  const int rp = threadIdx.x >> 4;
+  const int c16 = threadIdx.x & 15;
 #pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    int d = c16 * 8 + j;
-    uint pair = ((uint)(unsigned short)a.s[j]) |
-                (((uint)(unsigned short)b.s[j]) << 16);
-    *(uint*)(lds_tr + d * (TR_PITCH * 2) + r0 * 2) = pair;
-  }
-}
-
-__device__ __forceinline__ void write_tile32_rm(StageRegs r, char* lds_rm) {
-  if (blockDim.x > 256 && threadIdx.x >= 256) return;
-  int rp = threadIdx.x >> 4;
-  int c16 = threadIdx.x & 15;
-  int r0 = 2 * rp, r1 = 2 * rp + 1;
-  *(uint4v*)(lds_rm + r0 * (FA_D * 2) + swz16(r0, c16 * 16)) = r.v0;
-  *(uint4v*)(lds_rm + r1 * (FA_D * 2) + swz16(r1, c16 * 16)) = r.v1;
-}
-
-__device__ __forceinline__ void stage_tile32(const short* __restrict__ src,
-                                             long src_row0, long src_stride,
-                                             int rows_valid, char* lds_rm,
-                                             char* lds_tr) {
-  if (blockDim.x > 256 && threadIdx.x >= 256) return;
-  // thread t owns rows {2rp, 2rp+1} at 16B slot c16 (rp = t>>4, c16 = t&15):
-  // row-major: 2 x b128 writes; transposed: 8 x b32 (two k cols per write).
-  // NOTE: swz32 flips byte bits 4-5; a b32 write at (k=2rp)*2 has the pair
-  // within one 4-byte word only when the two k's share the swizzled word,
-  // which holds because swz32 only permutes 16-byte groups.
-  int rp = threadIdx.x >> 4;
-  int c16 = threadIdx.x & 15;
-  int r0 = 2 * rp, r1 = 2 * rp + 1;
-  int rr0 = r0 < rows_valid ? r0 : (rows_valid > 0 ? rows_valid - 1 : 0);
-  int rr1 = r1 < rows_valid ? r1 : (rows_valid > 0 ? rows_valid - 1 : 0);
-  uint4v v0 = *(const uint4v*)(src + (src_row0 + rr0) * src_stride + c16 * 8);
-  uint4v v1 = *(const uint4v*)(src + (src_row0 + rr1) * src_stride + c16 * 8);
-  *(uint4v*)(lds_rm + r0 * (FA_D * 2) + swz16(r0, c16 * 16)) = v0;
-  *(uint4v*)(lds_rm + r1 * (FA_D * 2) + swz16(r1, c16 * 16)) = v1;
-  union { uint4v u; short s[8]; } a, b;
-  a.u = v0; b.u = v1;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    int d = c16 * 8 + j;
-    uint pair = ((uint)(unsigned short)a.s[j]) |
-                (((uint)(unsigned short)b.s[j]) << 16);
-    *(uint*)(lds_tr + d * (TR_PITCH * 2) + r0 * 2) = pair;
-  }
+  for (int i = 0; i < NR; ++i)
+    *(uint4v*)(img + img_off(NR * rp + i, c16)) = r.v[i];
 }
 
 // ---------------------------------------------------------------------------
 // dK/dV kernel (8 waves over a 128-row kv block; see kernel comment)
-// LDS: Q rm 32KB + Qt/dOt transposed 36.9KB + lse/delta 512B — the P/dS
-// tiles live entirely in registers (pack + permlane32_swap repack).
+// LDS: 2 staging buffers x {Q 16 KB + dO 16 KB + lse/delta 512 B} = 65 KB
+// + 32 KB cross-wave exchange = 97 KB -- the P/dS tiles live entirely in
+// registers (pack + permlane32_swap repack).
 // ---------------------------------------------------------------------------
-#define TR_TILE_B (FA_D * TR_PITCH * 2)  // 10240 B
-
-// ---- 64-row tile staging (512 threads, 2-row pairs) ----------------------
-#define TR64_PITCH 72   // 144-byte rows: 16B-aligned, banks 4*(9d mod 16)
-#define TR64_TILE_B (FA_D * TR64_PITCH * 2)   // 18432 B
+#define BW64_BUF_B (2 * TILE64_B + 128 * 4)   // 33280 B per staging buffer
 #define BW64_LDS_Q 0
-#define BW64_LDS_DO (64 * FA_D * 2)
-#define BW64_LDS_QT (2 * 64 * FA_D * 2)
-#define BW64_LDS_DOT (2 * 64 * FA_D * 2 + TR64_TILE_B)
+#define BW64_LDS_DO TILE64_B
 // 128 floats: lse*log2(e) for the 64 q rows at [0..64), delta at [64..128)
-#define BW64_LDS_LD (2 * 64 * FA_D * 2 + 2 * TR64_TILE_B)
+#define BW64_LDS_LD (2 * TILE64_B)
 // cross-wave A-fragment exchange: 8 slots (kvg x q-half) x 4 frags x
-// 64 lanes x 16 B = 32 KB.  The kernel is VGPR-bound at 1 WG/CU (254
-// VGPRs -> 2 waves/SIMD), so this LDS is free occupancy-wise.
-#define BW64_LDS_X (BW64_LDS_LD + 128 * 4)
+// 64 lanes x 16 B = 32 KB.  The kernel is VGPR-bound at 1 WG/CU (2
+// waves/SIMD), so this LDS is free occupancy-wise.
+#define BW64_LDS_X (2 * BW64_BUF_B)
 #define BW64_X_SLOT(kvg, half, f) \
   ((((kvg) * 2 + (half)) * 4 + (f)) * 64 * 16)
-
-struct Stage64Regs { uint4v v0, v1; };
-
-__device__ __forceinline__ Stage64Regs load_tile64(
-    const short* __restrict__ src, long src_row0, long src_stride,
-    int rows_valid) {
-  int rp = threadIdx.x >> 4;        // 0..31 -> rows 2rp, 2rp+1 (0..63)
-  int c16 = threadIdx.x & 15;
-  int r0 = 2 * rp, r1 = 2 * rp + 1;
-  int rr0 = r0 < rows_valid ? r0 : (rows_valid > 0 ? rows_valid - 1 : 0);
-  int rr1 = r1 < rows_valid ? r1 : (rows_valid > 0 ? rows_valid - 1 : 0);
-  Stage64Regs r;
-  r.v0 = *(const uint4v*)(src + (src_row0 + rr0) * src_stride + c16 * 8);
-  r.v1 = *(const uint4v*)(src + (src_row0 + rr1) * src_stride + c16 * 8);
-  return r;
-}
-
-__device__ __forceinline__ void write_tile64(Stage64Regs r, char* lds_rm,
-                                             char* lds_tr) {
-  int rp = threadIdx.x >> 4;
-  int c16 = threadIdx.x & 15;
-  int r0 = 2 * rp, r1 = 2 * rp + 1;
-  *(uint4v*)(lds_rm + r0 * (FA_D * 2) + swz16(r0, c16 * 16)) = r.v0;
-  *(uint4v*)(lds_rm + r1 * (FA_D * 2) + swz16(r1, c16 * 16)) = r.v1;
-  union { uint4v u; short s[8]; } a, b;
-  a.u = r.v0; b.u = r.v1;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    int d = c16 * 8 + j;
-    uint pair = ((uint)(unsigned short)a.s[j]) |
-                (((uint)(unsigned short)b.s[j]) << 16);
-    *(uint*)(lds_tr + d * (TR64_PITCH * 2) + r0 * 2) = pair;
-  }
-}
-
-__device__ __forceinline__ void stage_tile64(const short* __restrict__ src,
-                                             long src_row0, long src_stride,
-                                             int rows_valid, char* lds_rm,
-                                             char* lds_tr) {
-  write_tile64(load_tile64(src, src_row0, src_stride, rows_valid), lds_rm,
-               lds_tr);
-}
+#define BW64_LDS_TOTAL (BW64_LDS_X + 8 * 4 * 64 * 16)   // 99328 B
 
 extern "C" __global__ void __launch_bounds__(512, 2)
 fa_bwd_dkdv_kernel(const short* __restrict__ qp, const short* __restrict__ kp,
@@ -275,7 +190,6 @@ fa_bwd_dkdv_kernel(const short* __restrict__ qp, const short* __restrict__ kp,
   f32x16 dv_acc[2] = {};
   f32x16 dk_acc[2] = {};
 
-  float* ld_sm = (float*)(smem + BW64_LDS_LD);
   // threads 0..63 fetch lse (pre-scaled by log2 e), 64..127 delta
   auto load_ld = [&](int qt0) -> float {
     int qg = qt0 + (threadIdx.x & 63);
@@ -284,8 +198,8 @@ fa_bwd_dkdv_kernel(const short* __restrict__ qp, const short* __restrict__ kp,
     if (threadIdx.x < 128) return deltap[lse_base + qc];
     return 0.f;
   };
-  auto write_ld = [&](float v) {
-    if (threadIdx.x < 128) ld_sm[threadIdx.x] = v;
+  auto write_ld = [&](float v, char* buf) {
+    if (threadIdx.x < 128) ((float*)(buf + BW64_LDS_LD))[threadIdx.x] = v;
   };
 
   const float s2 = scale * LOG2E;
@@ -298,19 +212,38 @@ fa_bwd_dkdv_kernel(const short* __restrict__ qp, const short* __restrict__ kp,
     q_end = qe < S ? qe : S;
   }
 
-  stage_tile64(qp + q_base, q_start, q_ss, S - q_start, smem + BW64_LDS_Q,
-               smem + BW64_LDS_QT);
-  stage_tile64(dop + do_base, q_start, do_ss, S - q_start, smem + BW64_LDS_DO,
-               smem + BW64_LDS_DOT);
-  write_ld(load_ld(q_start));
+  write_tile64(load_tile64<2>(qp + q_base, q_start, q_ss, S - q_start),
+               smem + BW64_LDS_Q);
+  write_tile64(load_tile64<2>(dop + do_base, q_start, do_ss, S - q_start),
+               smem + BW64_LDS_DO);
+  write_ld(load_ld(q_start), smem);
 
-  Stage64Regs nq, ndo;
+  // Two staging buffers, two barriers per 64 q rows:
+  //   barrier A: buffer `cur` (written during the previous iteration) is
+  //     visible, and every wave has finished the previous consume, so the
+  //     exchange slots and buffer cur^1 are free;
+  //   barrier B: the produced A fragments are visible.
+  // The next tile's global loads are issued right after A and land in
+  // buffer cur^1 after the consume — nobody reads that buffer before the
+  // next barrier A, so no third barrier is needed.
+  // lane-dependent parts of the LDS read addresses (mfma.h): tile row
+  // `col` for the row reads; this wave's d-half (a 128-byte, i.e.
+  // 8-chunk, column offset: an XOR on the chunk index) for the transposed
+  // reads
+  const int row_base = img_row_base(col, hi);
+  const int tr_base = img_tr_base(lane) ^ (dhalf * 128);
+  StageRegs<2> nq, ndo;
   float nld = 0.f;
-  for (int q0 = q_start; q0 < q_end; q0 += 64) {
+  int cur = 0;
+  for (int q0 = q_start; q0 < q_end; q0 += 64, cur ^= 1) {
+    const int sb_off = cur * BW64_BUF_B;
+    const float* ld_sm = (const float*)(smem + sb_off + BW64_LDS_LD);
+    const int rowb = row_base + sb_off;
+    const int trb = tr_base + sb_off;
     __syncthreads();
     if (q0 + 64 < q_end) {
-      nq = load_tile64(qp + q_base, q0 + 64, q_ss, S - q0 - 64);
-      ndo = load_tile64(dop + do_base, q0 + 64, do_ss, S - q0 - 64);
+      nq = load_tile64<2>(qp + q_base, q0 + 64, q_ss, S - q0 - 64);
+      ndo = load_tile64<2>(dop + do_base, q0 + 64, do_ss, S - q0 - 64);
       nld = load_ld(q0 + 64);
     }
     // ---- PRODUCE: this wave computes S^T/dP^T for q-half = dhalf ONLY.
@@ -327,7 +260,6 @@ fa_bwd_dkdv_kernel(const short* __restrict__ qp, const short* __restrict__ kp,
           (!causal || (qh0 + 31 >= kv0)) && qh0 < S &&
           (window <= 0 || qh0 < kv0 + 31 + window);
       if (produce) {
-        const int rm_row = half * 32 + col;  // row inside the 64-row tile
         const int my_kv = kv0 + col;         // this lane's kv column
 
         // S^T2[q][kv]: A = Q rows (B-layout frag doubles as A: lane=q),
@@ -337,11 +269,9 @@ fa_bwd_dkdv_kernel(const short* __restrict__ qp, const short* __restrict__ kp,
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
           frag_u qfr, dofr;
-          qfr.u4 = *(const uint4v*)(smem + BW64_LDS_Q + rm_row * (FA_D * 2)
-                                    + swz16(rm_row, (c * 16 + hi * 8) * 2));
+          qfr.u4 = img_row_read(smem + BW64_LDS_Q, rowb + half * (32 * IMG_ROW_B), c);
           st = mfma_bf16(qfr.bf, kf[c].bf, st);
-          dofr.u4 = *(const uint4v*)(smem + BW64_LDS_DO + rm_row * (FA_D * 2)
-                                     + swz16(rm_row, (c * 16 + hi * 8) * 2));
+          dofr.u4 = img_row_read(smem + BW64_LDS_DO, rowb + half * (32 * IMG_ROW_B), c);
           dpt = mfma_bf16(dofr.bf, vf[c].bf, dpt);
         }
 
@@ -357,17 +287,31 @@ fa_bwd_dkdv_kernel(const short* __restrict__ qp, const short* __restrict__ kp,
           *(float4*)(dlt_v + 4 * g) =
               *(const float4*)(ld_sm + 64 + half * 32 + 8 * g + 4 * hi);
         }
+        // wave-uniform (as in the forward kernel): the 32q x 32kv sub-tile
+        // needs the per-element predicate only if it touches the causal
+        // diagonal, the end of the sequence or the window's band edge;
+        // interior tiles skip it
+        const bool need_mask =
+            (causal && kv0 + 31 > qh0) || kv0 + 31 >= S || qh0 + 31 >= S ||
+            (window > 0 && qh0 + 31 >= kv0 + window);
+        // (the branch holds only the selects that zero masked p's: two
+        // full copies of the p/dS loop made the register allocator spill)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          int ql = half * 32 + acc_row(r, hi);
-          int qg = q0 + ql;
-          bool masked = (causal && my_kv > qg) || my_kv >= S || qg >= S ||
-              (window > 0 && qg >= my_kv + window);
-          float p =
-              masked ? 0.f : __builtin_amdgcn_exp2f(st[r] * s2 - lse_v[r]);
-          st[r] = p;
-          dpt[r] = p * (dpt[r] - dlt_v[r]);
+        for (int r = 0; r < 16; ++r)
+          st[r] = __builtin_amdgcn_exp2f(st[r] * s2 - lse_v[r]);
+        if (need_mask) {
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            int ql = half * 32 + acc_row(r, hi);
+            int qg = q0 + ql;
+            // bitwise |: plain compares + one select, no per-element branch
+            bool masked = ((causal != 0) & (my_kv > qg)) | (my_kv >= S) |
+                (qg >= S) | ((window > 0) & (qg >= my_kv + window));
+            st[r] = masked ? 0.f : st[r];
+          }
         }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) dpt[r] = st[r] * (dpt[r] - dlt_v[r]);
 
         // repack accumulator rows (q) into A-fragment k-dim in REGISTERS
         // (same pack pairs + permlane32_swap as the forward kernel's P
@@ -425,19 +369,18 @@ fa_bwd_dkdv_kernel(const short* __restrict__ qp, const short* __restrict__ kp,
           (window > 0 && qh0 >= kv0 + 31 + window)) continue;
 
       // prefetch the dV/dK B fragments first — independent of the slot
-      // reads, so all 12 b128 LDS loads pipeline into one counted wait
+      // reads, so all LDS loads pipeline into one counted wait.  They are
+      // transposed reads of the SAME image the producer reads row-wise;
+      // the guard above is wave-uniform, so all 64 lanes are active here.
       frag_u dofr[2][2], qfr2[2][2];
 #pragma unroll
       for (int cq = 0; cq < 2; ++cq)
 #pragma unroll
         for (int nb = 0; nb < 2; ++nb) {
-          int d = dhalf * 64 + nb * 32 + col;
-          dofr[cq][nb].u4 = *(const uint4v*)(smem + BW64_LDS_DOT
-                                             + d * (TR64_PITCH * 2)
-                                             + (half * 32 + cq * 16 + hi * 8) * 2);
-          qfr2[cq][nb].u4 = *(const uint4v*)(smem + BW64_LDS_QT
-                                             + d * (TR64_PITCH * 2)
-                                             + (half * 32 + cq * 16 + hi * 8) * 2);
+          dofr[cq][nb].u4 = img_tr_read(smem + BW64_LDS_DO, trb,
+                                        half * 32 + cq * 16, nb * 32);
+          qfr2[cq][nb].u4 = img_tr_read(smem + BW64_LDS_Q, trb,
+                                        half * 32 + cq * 16, nb * 32);
         }
       frag_u pA[2], dA[2];
       const char* xb = smem + BW64_LDS_X;
@@ -457,11 +400,11 @@ fa_bwd_dkdv_kernel(const short* __restrict__ qp, const short* __restrict__ kp,
       __builtin_amdgcn_s_setprio(0);
     }
 
-    __syncthreads();
     if (q0 + 64 < q_end) {
-      write_tile64(nq, smem + BW64_LDS_Q, smem + BW64_LDS_QT);
-      write_tile64(ndo, smem + BW64_LDS_DO, smem + BW64_LDS_DOT);
-      write_ld(nld);
+      char* nxt = smem + (cur ^ 1) * BW64_BUF_B;
+      write_tile64(nq, nxt + BW64_LDS_Q);
+      write_tile64(ndo, nxt + BW64_LDS_DO);
+      write_ld(nld, nxt);
     }
   }
 
@@ -515,11 +458,14 @@ fa_bwd_dkdv_kernel(const short* __restrict__ qp, const short* __restrict__ kp,
 
 // ---------------------------------------------------------------------------
 // dQ kernel: 4 waves, wave owns q rows [q0 + 32*wid, +32)
-// LDS: K rm 8KB + Kt 8KB + V rm 8KB + per-wave dS tiles 4*2.5KB = 34KB
+// LDS: 2 staging buffers x {K 16 KB + V 16 KB} (64-row kv tiles) = 64 KB;
+// the epilogue's 4 per-wave 32x128 transpose tiles (32 KB) reuse it.
+// 2 WG/CU -> 128 KB of the CU's 160 KB.
 // ---------------------------------------------------------------------------
+#define DQ_BUF_B (2 * TILE64_B)   // 32768 B per staging buffer
 #define DQ_LDS_K 0
-#define DQ_LDS_KT (32 * FA_D * 2)
-#define DQ_LDS_V (32 * FA_D * 2 + TR_TILE_B)
+#define DQ_LDS_V TILE64_B
+#define DQ_LDS_TOTAL (2 * DQ_BUF_B)   // 65536 B
 
 extern "C" __global__ void __launch_bounds__(256, 2)
 fa_bwd_dq_kernel(const short* __restrict__ qp, const short* __restrict__ kp,
@@ -579,59 +525,88 @@ fa_bwd_dq_kernel(const short* __restrict__ qp, const short* __restrict__ kp,
       : 0;
   const float s2 = scale * LOG2E;
 
-  stage_tile32(kp + k_base, kv_begin, k_ss, S - kv_begin, smem + DQ_LDS_K,
-               smem + DQ_LDS_KT);
-  write_tile32_rm(load_tile32(vp + v_base, kv_begin, v_ss, S - kv_begin),
-                  smem + DQ_LDS_V);
+  write_tile64(load_tile64<4>(kp + k_base, kv_begin, k_ss, S - kv_begin),
+               smem + DQ_LDS_K);
+  write_tile64(load_tile64<4>(vp + v_base, kv_begin, v_ss, S - kv_begin),
+               smem + DQ_LDS_V);
 
-  StageRegs nk, nv;
-  for (int kv0 = kv_begin; kv0 < kv_end; kv0 += 32) {
+  // 64-row kv tiles in two staging buffers, ONE barrier per tile: it makes
+  // buffer `cur` visible and guarantees every wave has left buffer cur^1
+  // (read during the previous iteration), which this iteration refills
+  // after its compute.  Each tile is consumed as two 32-row halves in
+  // ascending kv order, so dq_acc accumulates in the same order as with
+  // 32-row tiles.
+  const int row_base = img_row_base(col, hi);
+  const int tr_base = img_tr_base(lane);
+  StageRegs<4> nk, nv;
+  int cur = 0;
+  for (int kv0 = kv_begin; kv0 < kv_end; kv0 += 64, cur ^= 1) {
+    const int rowb = row_base + cur * DQ_BUF_B;
+    const int trb = tr_base + cur * DQ_BUF_B;
     __syncthreads();
-    if (kv0 + 32 < kv_end) {
-      nk = load_tile32(kp + k_base, kv0 + 32, k_ss, S - kv0 - 32);
-      nv = load_tile32(vp + v_base, kv0 + 32, v_ss, S - kv0 - 32);
+    if (kv0 + 64 < kv_end) {
+      nk = load_tile64<4>(kp + k_base, kv0 + 64, k_ss, S - kv0 - 64);
+      nv = load_tile64<4>(vp + v_base, kv0 + 64, v_ss, S - kv0 - 64);
     }
-    const bool wave_active = (!causal || (kv0 <= q0 + 31)) &&
-        (window <= 0 || kv0 + 31 + window > q0);
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+      const int kvh0 = kv0 + half * 32;
+      // all guards here are wave-uniform (loop bounds and q0 come from
+      // scalars / readfirstlane): the transposed reads below need all 64
+      // lanes active
+      const bool wave_active = kvh0 < kv_end &&
+          (!causal || (kvh0 <= q0 + 31)) &&
+          (window <= 0 || kvh0 + 31 + window > q0);
+      if (!wave_active) continue;
 
-    if (wave_active) {
-      // S^T[k][q]: A = K rows (LDS rm, row k=col), B = Q^T (regs)
+      // S^T[k][q]: A = K rows (LDS image, row k=col), B = Q^T (regs)
       f32x16 st = {};
       f32x16 dpt = {};
 #pragma unroll
       for (int c = 0; c < 8; ++c) {
         frag_u kfr;
-        kfr.u4 = *(const uint4v*)(smem + DQ_LDS_K + col * (FA_D * 2)
-                                  + swz16(col, (c * 16 + hi * 8) * 2));
+        kfr.u4 = img_row_read(smem + DQ_LDS_K, rowb + half * (32 * IMG_ROW_B), c);
         st = mfma_bf16(kfr.bf, qf[c].bf, st);
         frag_u vfr;
-        vfr.u4 = *(const uint4v*)(smem + DQ_LDS_V + col * (FA_D * 2)
-                                  + swz16(col, (c * 16 + hi * 8) * 2));
+        vfr.u4 = img_row_read(smem + DQ_LDS_V, rowb + half * (32 * IMG_ROW_B), c);
         dpt = mfma_bf16(vfr.bf, dof[c].bf, dpt);
       }
 
+      // wave-uniform: the per-element predicate is needed only when the
+      // 32kv x 32q sub-tile touches the causal diagonal, the end of the
+      // sequence or the window's band edge
+      const bool need_mask =
+          (causal && kvh0 + 31 > q0) || kvh0 + 31 >= S || q0 + 31 >= S ||
+          (window > 0 && kvh0 <= q0 + 31 - window);
+      // (the branch holds only the selects that zero masked p's, which
+      // keeps register pressure where it was)
+#pragma unroll
+      for (int r = 0; r < 16; ++r)
+        st[r] = __builtin_amdgcn_exp2f(st[r] * s2 - lse2);
+      if (need_mask) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          int kg = kvh0 + acc_row(r, hi);
+          // bitwise |: plain compares + one select, no per-element branch
+          bool masked = ((causal != 0) & (kg > my_q)) | (kg >= S) |
+              (my_q >= S) | ((window > 0) & (kg <= my_q - window));
+          st[r] = masked ? 0.f : st[r];
+        }
+      }
       f32x16 dst;
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        int kg = kv0 + acc_row(r, hi);
-        bool masked = (causal && kg > my_q) || kg >= S || my_q >= S ||
-            (window > 0 && kg <= my_q - window);
-        float p = masked ? 0.f : __builtin_amdgcn_exp2f(st[r] * s2 - lse2);
-        dst[r] = p * (dpt[r] - dlt);
-      }
+      for (int r = 0; r < 16; ++r) dst[r] = st[r] * (dpt[r] - dlt);
 
-      // prefetch the 8 Kt B-fragments (independent of the pack below —
-      // the b128 LDS reads land under the pack VALU)
+      // prefetch the 8 K B-fragments (independent of the pack below — the
+      // LDS reads land under the pack VALU): transposed reads of the same
+      // K image the S^T mfmas read row-wise
       frag_u kfr2[2][4];
 #pragma unroll
       for (int ck = 0; ck < 2; ++ck)
 #pragma unroll
-        for (int nb = 0; nb < 4; ++nb) {
-          int d = nb * 32 + col;
-          kfr2[ck][nb].u4 = *(const uint4v*)(smem + DQ_LDS_KT
-                                             + d * (TR_PITCH * 2)
-                                             + (ck * 16 + hi * 8) * 2);
-        }
+        for (int nb = 0; nb < 4; ++nb)
+          kfr2[ck][nb].u4 = img_tr_read(smem + DQ_LDS_K, trb,
+                                        half * 32 + ck * 16, nb * 32);
 
       // repack dS accumulator rows (kv) into A-fragment k-dim in
       // REGISTERS (lane dim q already in place) — same pack pairs +
@@ -656,7 +631,7 @@ fa_bwd_dq_kernel(const short* __restrict__ qp, const short* __restrict__ kp,
       }
 
       // dQ[q][d] += sum_k dS[q][k] K[k][d]
-      //   A = dS (registers, lane=q), B = K[k][d] via Kt rows d
+      //   A = dS (registers, lane=q), B = K[k][d] (transposed reads)
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int ck = 0; ck < 2; ++ck) {
@@ -668,10 +643,10 @@ fa_bwd_dq_kernel(const short* __restrict__ qp, const short* __restrict__ kp,
       __builtin_amdgcn_s_setprio(0);
     }
 
-    __syncthreads();
-    if (kv0 + 32 < kv_end) {
-      write_tile32(nk, smem + DQ_LDS_K, smem + DQ_LDS_KT);
-      write_tile32_rm(nv, smem + DQ_LDS_V);
+    if (kv0 + 64 < kv_end) {
+      char* nxt = smem + (cur ^ 1) * DQ_BUF_B;
+      write_tile64(nk, nxt + DQ_LDS_K);
+      write_tile64(nv, nxt + DQ_LDS_V);
     }
   }
 
@@ -715,9 +690,10 @@ extern "C" void flash_attn_bwd_strided(
       (const short*)dout, (const short*)out, (float*)delta, rows, Hq, S,
       st[12], st[13], st[14], st[9], st[10], st[11]);
   dim3 gkv(Hq, (S + 127) / 128, B);
-  // staging (70,144 B) + A-fragment exchange (32,768 B) = 102,912 B; the
-  // kernel is VGPR-bound at 1 WG/CU so the extra LDS costs no occupancy
-  size_t lds1 = BW64_LDS_X + 8 * 4 * 64 * 16;
+  // 2 staging buffers (2 x 33,280 B) + A-fragment exchange (32,768 B) =
+  // 99,328 B; the kernel is VGPR-bound at 1 WG/CU so the LDS costs no
+  // occupancy
+  size_t lds1 = BW64_LDS_TOTAL;
   fa_bwd_dkdv_kernel<<<gkv, 512, lds1, stream>>>(
       (const short*)q, (const short*)k, (const short*)v, (const short*)dout,
       (const float*)lse, (const float*)delta, (short*)dk, (short*)dv, B, Hq,
@@ -725,9 +701,9 @@ extern "C" void flash_attn_bwd_strided(
       st[5], st[6], st[7], st[8], st[12], st[13], st[14], st[18], st[19],
       st[20], st[21], st[22], st[23]);
   dim3 gq(Hq, (S + 127) / 128, B);
-  // staging layout needs 26.6 KB; the epilogue reuses LDS as 4 per-wave
-  // 32x128 transpose tiles = 32 KB, which dominates
-  size_t lds2 = 4 * 32 * FA_D * 2;
+  // 2 staging buffers x (K + V 64-row tiles) = 64 KB; the epilogue's 4
+  // per-wave 32x128 transpose tiles (32 KB) reuse it.  64 KB keeps 2 WG/CU.
+  size_t lds2 = DQ_LDS_TOTAL;
   fa_bwd_dq_kernel<<<gq, 256, lds2, stream>>>(
       (const short*)q, (const short*)k, (const short*)v, (const short*)dout,
       (const float*)lse, (const float*)delta, (short*)dq, B, Hq, Hkv, S,
