@@ -4,19 +4,25 @@
 // reference kernels/flash_attn.py:18,51-63).  MI355X-first design per
 // cdna_hip_programming.md §B:
 //   * 8 waves/WG, each wave owns 32 q rows (WG = 256 q rows); KV tiles of
-//     64 double-buffered in LDS with the (row&7)<<4 XOR swizzle (G4).
+//     64 rows in two staging buffers, one barrier per tile.  K and V are
+//     each stored ONCE per tile in the dual-use LDS image of mfma.h
+//     (256-byte rows, 16-byte chunks XORed by img_off): K is read row-wise
+//     (ds_read_b128, A operand of QK^T), V transposed
+//     (ds_read_b64_tr_b16, A operand of PV).
 //   * swapped QK^T — mfma(A=K, B=Q^T) — so each lane's softmax stats are
 //     for ONE q row (l&31): row max / rescale / denom are lane-local
 //     (+ one shfl_xor with the partner half-wave).
 //   * P is repacked to bf16 PV B-fragments with pack_bf16x2 +
 //     v_permlane32_swap (T12/T21 primitive).
 //   * O is accumulated TRANSPOSED (O^T[d][q], q = lane) so the online
-//     rescale is a per-lane scalar multiply; V is staged transposed (Vt).
+//     rescale is a per-lane scalar multiply; the epilogue transposes it
+//     back through LDS and stores whole 256-byte rows.
 //   * GQA: kv head = q head / (Hq/Hkv); causal masking per element on
 //     diagonal tiles, whole-tile skip below the diagonal.
 //
-// Layouts: q,k,v,out (B, H, S, D) bf16 contiguous, D = 128; lse (B,Hq,S)
-// f32 (natural-log row logsumexp, saved for backward).
+// Layouts: q,k,v,out (B, H, S, D)-indexed bf16 with any (batch, head, seq)
+// strides and a dense d, D = 128; lse (B,Hq,S) f32 contiguous
+// (natural-log row logsumexp, saved for backward).
 
 #include "common.h"
 #include "mfma.h"
@@ -29,14 +35,17 @@
 #define LOG2E 1.4426950408889634f
 #define NEG_INF (-1e30f)
 
-// LDS: double-buffered K [64][128] bf16 (256B rows, swz16 = conflict-free
-// b128 reads) and Vt [128][72] bf16 (144B padded rows: 16B-aligned, and
-// 36*d = 4*(9d mod 16) banks are distinct within every b128 lane group
-// since 9 is coprime to 16 -> conflict-free, no swizzle needed)
-#define K_TILE_B (FA_KV * FA_D * 2)    // 16 KB
-#define VT_PITCH 72
-#define VT_TILE_B (FA_D * VT_PITCH * 2)  // 18 KB
+// LDS: two staging buffers, each one K image + one V image of a 64-row tile
+// (mfma.h dual-use image, 256-byte rows).  After the kv loop the same
+// memory holds the 8 per-wave 32x128 O tiles of the epilogue.
+#define FA_TILE_B (FA_KV * IMG_ROW_B)   // 16 KB
+#define FA_BUF_B (2 * FA_TILE_B)        // K image, then V image
+#define FA_LDS_V FA_TILE_B
+#define FA_LDS_TOTAL (2 * FA_BUF_B)     // 65,536 B
 
+// The second launch-bound is HIP's minimum waves per SIMD, not blocks per
+// CU: 2 waves/SIMD is exactly one 8-wave workgroup per CU.  The 64 KB of
+// LDS would admit a second workgroup; the ~250 VGPRs per lane do not.
 extern "C" __global__ void __launch_bounds__(512, 2)
 flash_fwd_kernel(const short* __restrict__ qp, const short* __restrict__ kp,
                  const short* __restrict__ vp, short* __restrict__ op,
@@ -53,13 +62,6 @@ flash_fwd_kernel(const short* __restrict__ qp, const short* __restrict__ kp,
   // [i - window + 1, i] (causal implied); whole tiles outside the band
   // are skipped, boundary tiles masked per element.
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  // THREE rotating K/Vt buffers: tile t is read from buf t%3 while t+1 is
-  // written into (t+1)%3, whose previous readers (tile t-2) finished two
-  // barriers ago -> ONE barrier per tile instead of two.
-  auto kbuf = [&](int i) { return smem + (size_t)i * K_TILE_B; };
-  auto vbuf = [&](int i) {
-    return smem + 3 * K_TILE_B + (size_t)i * VT_TILE_B;
-  };
 
   const int lane = threadIdx.x & 63;
   // readfirstlane: provably wave-uniform -> scalar branches for the
@@ -112,10 +114,11 @@ flash_fwd_kernel(const short* __restrict__ qp, const short* __restrict__ kp,
 
   const float s2 = scale * LOG2E;
 
-  // ---- staging: thread t owns K/V rows {2rp, 2rp+1} at 16B slot c16 ----
-  // (rp = t>>4 in 0..31, c16 = t&15).  K: 2 x ds_write_b128 swizzled;
-  // V: the row PAIR transposes into 8 x b32 writes (two k-columns per
-  // write) instead of 16 scalar b16 scatters.
+  // ---- staging: thread t owns K/V rows {2rp, 2rp+1} at 16-byte chunk
+  // c16 (rp = t>>4 in 0..31, c16 = t&15): 4 coalesced b128 global loads
+  // and 4 ds_write_b128 per tile, K and V alike.  Rows past the end of the
+  // sequence are CLAMPED, never skipped: every image row always holds
+  // data, so the transposed reads run with all lanes active.
   const int tid = threadIdx.x;
   const int st_rp = tid >> 4;
   const int st_c16 = tid & 15;
@@ -133,34 +136,46 @@ flash_fwd_kernel(const short* __restrict__ qp, const short* __restrict__ kp,
   };
 
   auto write_tile = [&](int buf) {
-    *(uint4v*)(kbuf(buf) + swz16(st_r0, st_c16 * 16)
-               + st_r0 * (FA_D * 2)) = kreg[0];
-    *(uint4v*)(kbuf(buf) + swz16(st_r1, st_c16 * 16)
-               + st_r1 * (FA_D * 2)) = kreg[1];
-    union { uint4v u; short s[8]; } a, b;
-    a.u = vreg[0];
-    b.u = vreg[1];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      int d = st_c16 * 8 + j;
-      uint pair = ((uint)(unsigned short)a.s[j]) |
-                  (((uint)(unsigned short)b.s[j]) << 16);
-      *(uint*)(vbuf(buf) + d * (VT_PITCH * 2) + st_r0 * 2) = pair;
-    }
+    char* kimg = smem + buf * FA_BUF_B;
+    char* vimg = kimg + FA_LDS_V;
+    *(uint4v*)(kimg + img_off(st_r0, st_c16)) = kreg[0];
+    *(uint4v*)(kimg + img_off(st_r1, st_c16)) = kreg[1];
+    *(uint4v*)(vimg + img_off(st_r0, st_c16)) = vreg[0];
+    *(uint4v*)(vimg + img_off(st_r1, st_c16)) = vreg[1];
   };
 
-  issue_loads(t_begin);
-  write_tile(t_begin % 3);
-  __syncthreads();
+  // lane-dependent parts of the LDS read addresses (mfma.h): tile row `col`
+  // for the K row reads, the 4x16 block pattern for the V transposed reads
+  const int row_base = img_row_base(col, hi);
+  const int tr_base = img_tr_base(lane) + FA_LDS_V;
 
-  for (int t = t_begin; t < ntiles; ++t) {
+  issue_loads(t_begin);
+  write_tile(0);
+  __syncthreads();
+  // Q must have LANDED before the loop.  Left to itself the compiler sinks
+  // the Q loads below the barrier and puts their vmcnt waits into the
+  // loop's QK^T burst, where every iteration after the first they wait
+  // for the NEXT tile's K/V loads issued a few instructions earlier: the
+  // global latency the early issue is meant to hide.
+#pragma unroll
+  for (int c = 0; c < 8; ++c) asm volatile("" : "+v"(qf[c].u4));
+
+  // Two staging buffers, ONE barrier per tile: tile t is read from buffer
+  // `cur` while t+1 is written into cur^1 at the end of the iteration.  A
+  // wave that gets there has passed the barrier that ended iteration t-1,
+  // so every wave has finished reading cur^1 (tile t-1).
+  int cur = 0;
+  for (int t = t_begin; t < ntiles; ++t, cur ^= 1) {
     const int kv0 = t * FA_KV;
-    const int cur = t % 3;
     if (t + 1 < ntiles) issue_loads(t + 1);
 
+    // wave-uniform (wid is readfirstlane-derived, the rest kernel
+    // arguments): the transposed reads below need all 64 lanes active
     const bool wave_active = kv0 < my_kv_end &&
         (window <= 0 || kv0 + FA_KV > my_kv_begin);
     if (wave_active) {
+      const int rowb = row_base + cur * FA_BUF_B;
+      const int trb = tr_base + cur * FA_BUF_B;
       // ---- QK^T: S^T[k][q] = sum_d K[k][d] Q^T[d][q] ------------------
       // All 16 K fragments are prefetched into registers BEFORE the mfma
       // burst (T3/T4): with ds_reads issued only 1-2 mfmas ahead the
@@ -170,13 +185,11 @@ flash_fwd_kernel(const short* __restrict__ qp, const short* __restrict__ kp,
       f32x16 acc[2] = {};
       frag_u kfr[2][8];
 #pragma unroll
-      for (int kb = 0; kb < 2; ++kb) {
-        int row = col + 32 * kb;
+      for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
         for (int c = 0; c < 8; ++c)
-          kfr[kb][c].u4 = *(const uint4v*)(kbuf(cur) + row * (FA_D * 2)
-                                           + swz16(row, (c * 16 + hi * 8) * 2));
-      }
+          kfr[kb][c].u4 =
+              img_row_read(smem, rowb + kb * (32 * IMG_ROW_B), c);
       __builtin_amdgcn_s_setprio(1);  // T5: keep the matrix pipe fed
 #pragma unroll
       for (int kb = 0; kb < 2; ++kb)
@@ -185,23 +198,39 @@ flash_fwd_kernel(const short* __restrict__ qp, const short* __restrict__ kp,
           acc[kb] = mfma_bf16(kfr[kb][c].bf, qf[c].bf, acc[kb]);
       __builtin_amdgcn_s_setprio(0);
 
+      // ---- V^T fragments of the whole tile: transposed reads of the V
+      // image, vfr[c16][nb] = V[16*c16 + 8*hi + j][32*nb + col].  They take
+      // over the registers the K fragments leave and land under the
+      // softmax below.
+      frag_u vfr[4][4];
+#pragma unroll
+      for (int c16 = 0; c16 < 4; ++c16)
+#pragma unroll
+        for (int nb = 0; nb < 4; ++nb)
+          vfr[c16][nb].u4 = img_tr_read(smem, trb, 16 * c16, 32 * nb);
+
       // ---- online softmax (exp2 domain), lane-local per q row ---------
       float sc[2][16];
-      const bool need_mask =
-          (causal && kv0 + FA_KV > qw0) || (kv0 + FA_KV > S) ||
-          (window > 0 && kv0 < qw0 + FA_QW - 1 - window + 1 + FA_KV);
 #pragma unroll
       for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          float v = acc[kb][r] * s2;
-          if (need_mask) {
+        for (int r = 0; r < 16; ++r) sc[kb][r] = acc[kb][r] * s2;
+      const bool need_mask =
+          (causal && kv0 + FA_KV > qw0) || (kv0 + FA_KV > S) ||
+          (window > 0 && kv0 < qw0 + FA_QW - 1 - window + 1 + FA_KV);
+      // (the branch holds only the selects; interior tiles skip it)
+      if (need_mask) {
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
             int kg = kv0 + 32 * kb + acc_row(r, hi);
-            if ((causal && kg > my_q) || kg >= S ||
-                (window > 0 && kg <= my_q - window)) v = NEG_INF;
+            // bitwise |: plain compares + one select per element
+            bool masked = ((causal != 0) & (kg > my_q)) | (kg >= S) |
+                ((window > 0) & (kg <= my_q - window));
+            sc[kb][r] = masked ? NEG_INF : sc[kb][r];
           }
-          sc[kb][r] = v;
-        }
+      }
 
       float mt = NEG_INF;
 #pragma unroll
@@ -217,90 +246,88 @@ flash_fwd_kernel(const short* __restrict__ qp, const short* __restrict__ kp,
       float m_eff = fmaxf(m_new, -1e28f);
       float alpha = __builtin_amdgcn_exp2f(m_run - m_eff);  // 0 when m_run=-1e30
       m_run = m_new;
-
-      float psum = 0.f;
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          float p = __builtin_amdgcn_exp2f(sc[kb][r] - m_eff);
-          sc[kb][r] = p;
-          psum += p;
-        }
-      psum += __shfl_xor(psum, 32, 64);
-      l_run = l_run * alpha + psum;
-
 #pragma unroll
       for (int nb = 0; nb < 4; ++nb) ot[nb] *= alpha;
 
-      // ---- pack P -> PV B-fragments (4 chunks of 16 k) ----------------
+      // ---- P = exp2(S - m) and its row sum; P chunk s (16 kv rows) is
+      // packed to the bf16 B fragment pf[s] of the PV mfmas ---------------
+      float psum = 0.f;
       frag_u pf[4];
+      auto p_chunk = [&](int s) {
+        const int kb = s >> 1, r0 = 8 * (s & 1);
 #pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-        for (int cc = 0; cc < 2; ++cc) {
-          uint b0 = pack_bf16x2(sc[kb][8 * cc + 0], sc[kb][8 * cc + 1]);
-          uint b1 = pack_bf16x2(sc[kb][8 * cc + 2], sc[kb][8 * cc + 3]);
-          uint b2 = pack_bf16x2(sc[kb][8 * cc + 4], sc[kb][8 * cc + 5]);
-          uint b3 = pack_bf16x2(sc[kb][8 * cc + 6], sc[kb][8 * cc + 7]);
-          {
-            auto r01 = __builtin_amdgcn_permlane32_swap(b0, b2, false, false);
-            b0 = r01[0]; b2 = r01[1];
-          }
-          {
-            auto r23 = __builtin_amdgcn_permlane32_swap(b1, b3, false, false);
-            b1 = r23[0]; b3 = r23[1];
-          }
-          frag_u& f = pf[2 * kb + cc];
-          f.u[0] = b0; f.u[1] = b1; f.u[2] = b2; f.u[3] = b3;
+        for (int j = 0; j < 8; ++j) {
+          float p = __builtin_amdgcn_exp2f(sc[kb][r0 + j] - m_eff);
+          sc[kb][r0 + j] = p;
+          psum += p;
         }
-
+        uint b0 = pack_bf16x2(sc[kb][r0 + 0], sc[kb][r0 + 1]);
+        uint b1 = pack_bf16x2(sc[kb][r0 + 2], sc[kb][r0 + 3]);
+        uint b2 = pack_bf16x2(sc[kb][r0 + 4], sc[kb][r0 + 5]);
+        uint b3 = pack_bf16x2(sc[kb][r0 + 6], sc[kb][r0 + 7]);
+        {
+          auto r01 = __builtin_amdgcn_permlane32_swap(b0, b2, false, false);
+          b0 = r01[0]; b2 = r01[1];
+        }
+        {
+          auto r23 = __builtin_amdgcn_permlane32_swap(b1, b3, false, false);
+          b1 = r23[0]; b3 = r23[1];
+        }
+        pf[s].u[0] = b0; pf[s].u[1] = b1; pf[s].u[2] = b2; pf[s].u[3] = b3;
+      };
       // ---- PV: O^T[d][q] += V^T[d][k] P^T[k][q] -----------------------
-      // Same batched-prefetch structure as QK, two d-blocks at a time
-      // (8 fragments = 32 VGPRs in flight).
 #pragma unroll
-      for (int np = 0; np < 2; ++np) {
-        frag_u vfr[2][4];
+      for (int s = 0; s < 4; ++s) p_chunk(s);
+      __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-        for (int ni = 0; ni < 2; ++ni) {
-          int d = 32 * (2 * np + ni) + col;
+      for (int nb = 0; nb < 4; ++nb)
 #pragma unroll
-          for (int c16 = 0; c16 < 4; ++c16)
-            vfr[ni][c16].u4 = *(const uint4v*)(vbuf(cur) + d * (VT_PITCH * 2)
-                                               + (c16 * 16 + hi * 8) * 2);
-        }
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-          for (int c16 = 0; c16 < 4; ++c16)
-            ot[2 * np + ni] =
-                mfma_bf16(vfr[ni][c16].bf, pf[c16].bf, ot[2 * np + ni]);
-        __builtin_amdgcn_s_setprio(0);
-      }
+        for (int c16 = 0; c16 < 4; ++c16)
+          ot[nb] = mfma_bf16(vfr[c16][nb].bf, pf[c16].bf, ot[nb]);
+      __builtin_amdgcn_s_setprio(0);
+      psum += __shfl_xor(psum, 32, 64);
+      l_run = l_run * alpha + psum;
     }
 
-    if (t + 1 < ntiles) write_tile((t + 1) % 3);
+    if (t + 1 < ntiles) write_tile(cur ^ 1);
     __syncthreads();
   }
 
   // ---- epilogue: normalize, store O (transposed back) and LSE ---------
-  if (my_q >= S) return;
   float inv_l = l_run > 0.f ? 1.f / l_run : 0.f;
-  long o_row = (long)b * o_bs + (long)h * o_hs + (long)my_q * o_ss;
+  long o_base = (long)b * o_bs + (long)h * o_hs;
+  // The loop's last barrier has passed, so the staging buffers are free:
+  // each wave transposes its 32x128 O tile through 8 KB of them (image
+  // rows = q rows) and stores whole 256-byte rows, 4 rows per b128 store
+  // instruction, instead of 8 bytes per lane at a row stride.
+  if (qw0 < S) {
+    char* otile = smem + wid * (FA_QW * IMG_ROW_B);
 #pragma unroll
-  for (int nb = 0; nb < 4; ++nb) {
+    for (int nb = 0; nb < 4; ++nb) {
 #pragma unroll
-    for (int rg = 0; rg < 4; ++rg) {
-      int d = 32 * nb + 8 * rg + 4 * hi;
-      uint w0 = pack_bf16x2(ot[nb][4 * rg + 0] * inv_l,
-                            ot[nb][4 * rg + 1] * inv_l);
-      uint w1 = pack_bf16x2(ot[nb][4 * rg + 2] * inv_l,
-                            ot[nb][4 * rg + 3] * inv_l);
-      uint2 st = {w0, w1};
-      *(uint2*)(op + o_row + d) = st;
+      for (int rg = 0; rg < 4; ++rg) {
+        // d = 32*nb + 8*rg + 4*hi .. +3: chunk 4*nb + rg, half hi
+        uint w0 = pack_bf16x2(ot[nb][4 * rg + 0] * inv_l,
+                              ot[nb][4 * rg + 1] * inv_l);
+        uint w1 = pack_bf16x2(ot[nb][4 * rg + 2] * inv_l,
+                              ot[nb][4 * rg + 3] * inv_l);
+        uint2 st = {w0, w1};
+        *(uint2*)(otile + img_off(col, 4 * nb + rg) + 8 * hi) = st;
+      }
+    }
+    __builtin_amdgcn_s_waitcnt(0);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      int p = lane + i * 64;
+      int row = p >> 4, c16 = p & 15;
+      int qg = qw0 + row;
+      if (qg < S) {
+        uint4v vv = *(const uint4v*)(otile + img_off(row, c16));
+        *(uint4v*)(op + o_base + (long)qg * o_ss + c16 * 8) = vv;
+      }
     }
   }
+  if (my_q >= S) return;
   if (hi == 0 && lsep) {
     // natural-log LSE: scores were in exp2 domain
     lsep[(long)(b * Hq + h) * S + my_q] =
@@ -313,7 +340,7 @@ extern "C" void flash_attn_fwd(const void* q, const void* k, const void* v,
                                int S, float scale, int causal,
                                hipStream_t stream) {
   dim3 grid(Hq, (S + FA_QBLK - 1) / FA_QBLK, B);
-  size_t lds = 3 * (K_TILE_B + VT_TILE_B);
+  size_t lds = FA_LDS_TOTAL;
   flash_fwd_kernel<<<grid, 512, lds, stream>>>(
       (const short*)q, (const short*)k, (const short*)v, (short*)out,
       (float*)lse, B, Hq, Hkv, S, scale, causal, 0,
@@ -329,7 +356,7 @@ extern "C" void flash_attn_fwd_strided(
     const long* st, hipStream_t stream) {
   // st = 12 longs: (bs, hs, ss) x (q, k, v, o)
   dim3 grid(Hq, (S + FA_QBLK - 1) / FA_QBLK, B);
-  size_t lds = 3 * (K_TILE_B + VT_TILE_B);
+  size_t lds = FA_LDS_TOTAL;
   flash_fwd_kernel<<<grid, 512, lds, stream>>>(
       (const short*)q, (const short*)k, (const short*)v, (short*)out,
       (float*)lse, B, Hq, Hkv, S, scale, causal, window,
@@ -343,7 +370,7 @@ extern "C" void flash_attn_fwd_window(const void* q, const void* k,
                                       float scale, int window,
                                       hipStream_t stream) {
   dim3 grid(Hq, (S + FA_QBLK - 1) / FA_QBLK, B);
-  size_t lds = 3 * (K_TILE_B + VT_TILE_B);
+  size_t lds = FA_LDS_TOTAL;
   flash_fwd_kernel<<<grid, 512, lds, stream>>>(
       (const short*)q, (const short*)k, (const short*)v, (short*)out,
       (float*)lse, B, Hq, Hkv, S, scale, 1, window,
