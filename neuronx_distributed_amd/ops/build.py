@@ -29,7 +29,7 @@ def _needs_build():
         return True
     lib_mtime = os.path.getmtime(LIB)
     deps = _sources() + [os.path.join(CSRC, h)
-                         for h in ("common.h", "mfma.h")]
+                         for h in os.listdir(CSRC) if h.endswith(".h")]
     return any(os.path.getmtime(s) > lib_mtime for s in deps)
 
 

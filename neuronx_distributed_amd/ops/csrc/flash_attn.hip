@@ -24,23 +24,19 @@
 // strides and a dense d, D = 128; lse (B,Hq,S) f32 contiguous
 // (natural-log row logsumexp, saved for backward).
 
-#include "common.h"
-#include "mfma.h"
+#include "flash_common.h"
 
-#define FA_D 128
 #define FA_QW 32       // q rows per wave
 #define FA_WAVES 8
 #define FA_QBLK (FA_QW * FA_WAVES)  // 256 q rows per workgroup
 #define FA_KV 64       // kv tile
-#define LOG2E 1.4426950408889634f
 #define NEG_INF (-1e30f)
 
 // LDS: two staging buffers, each one K image + one V image of a 64-row tile
 // (mfma.h dual-use image, 256-byte rows).  After the kv loop the same
 // memory holds the 8 per-wave 32x128 O tiles of the epilogue.
-#define FA_TILE_B (FA_KV * IMG_ROW_B)   // 16 KB
-#define FA_BUF_B (2 * FA_TILE_B)        // K image, then V image
-#define FA_LDS_V FA_TILE_B
+#define FA_BUF_B (2 * TILE64_B)         // K image, then V image
+#define FA_LDS_V TILE64_B
 #define FA_LDS_TOTAL (2 * FA_BUF_B)     // 65,536 B
 
 // The second launch-bound is HIP's minimum waves per SIMD, not blocks per
@@ -114,11 +110,11 @@ flash_fwd_kernel(const short* __restrict__ qp, const short* __restrict__ kp,
 
   const float s2 = scale * LOG2E;
 
-  // ---- staging: thread t owns K/V rows {2rp, 2rp+1} at 16-byte chunk
-  // c16 (rp = t>>4 in 0..31, c16 = t&15): 4 coalesced b128 global loads
-  // and 4 ds_write_b128 per tile, K and V alike.  Rows past the end of the
-  // sequence are CLAMPED, never skipped: every image row always holds
-  // data, so the transposed reads run with all lanes active.
+  // ---- staging: the NR = 2 case of load_tile64 / write_tile64
+  // (flash_common.h; same thread -> row/chunk map, same clamp-never-skip
+  // rule), kept by hand: going through the helpers changes this kernel's
+  // generated code (profiles/KERNEL_NOTES.md).  Thread t owns K/V rows
+  // {2rp, 2rp+1} at 16-byte chunk c16 (rp = t>>4, c16 = t&15).
   const int tid = threadIdx.x;
   const int st_rp = tid >> 4;
   const int st_c16 = tid & 15;
@@ -225,10 +221,8 @@ flash_fwd_kernel(const short* __restrict__ qp, const short* __restrict__ kp,
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
             int kg = kv0 + 32 * kb + acc_row(r, hi);
-            // bitwise |: plain compares + one select per element
-            bool masked = ((causal != 0) & (kg > my_q)) | (kg >= S) |
-                ((window > 0) & (kg <= my_q - window));
-            sc[kb][r] = masked ? NEG_INF : sc[kb][r];
+            sc[kb][r] = fa_masked<false>(kg, my_q, S, causal, window)
+                ? NEG_INF : sc[kb][r];
           }
       }
 
@@ -261,19 +255,7 @@ flash_fwd_kernel(const short* __restrict__ qp, const short* __restrict__ kp,
           sc[kb][r0 + j] = p;
           psum += p;
         }
-        uint b0 = pack_bf16x2(sc[kb][r0 + 0], sc[kb][r0 + 1]);
-        uint b1 = pack_bf16x2(sc[kb][r0 + 2], sc[kb][r0 + 3]);
-        uint b2 = pack_bf16x2(sc[kb][r0 + 4], sc[kb][r0 + 5]);
-        uint b3 = pack_bf16x2(sc[kb][r0 + 6], sc[kb][r0 + 7]);
-        {
-          auto r01 = __builtin_amdgcn_permlane32_swap(b0, b2, false, false);
-          b0 = r01[0]; b2 = r01[1];
-        }
-        {
-          auto r23 = __builtin_amdgcn_permlane32_swap(b1, b3, false, false);
-          b1 = r23[0]; b3 = r23[1];
-        }
-        pf[s].u[0] = b0; pf[s].u[1] = b1; pf[s].u[2] = b2; pf[s].u[3] = b3;
+        pf[s] = acc8_to_frag(sc[kb], r0);
       };
       // ---- PV: O^T[d][q] += V^T[d][k] P^T[k][q] -----------------------
 #pragma unroll
@@ -335,21 +317,6 @@ flash_fwd_kernel(const short* __restrict__ qp, const short* __restrict__ kp,
   }
 }
 
-extern "C" void flash_attn_fwd(const void* q, const void* k, const void* v,
-                               void* out, void* lse, int B, int Hq, int Hkv,
-                               int S, float scale, int causal,
-                               hipStream_t stream) {
-  dim3 grid(Hq, (S + FA_QBLK - 1) / FA_QBLK, B);
-  size_t lds = FA_LDS_TOTAL;
-  flash_fwd_kernel<<<grid, 512, lds, stream>>>(
-      (const short*)q, (const short*)k, (const short*)v, (short*)out,
-      (float*)lse, B, Hq, Hkv, S, scale, causal, 0,
-      (long)Hq * S * FA_D, (long)S * FA_D, FA_D,
-      (long)Hkv * S * FA_D, (long)S * FA_D, FA_D,
-      (long)Hkv * S * FA_D, (long)S * FA_D, FA_D,
-      (long)Hq * S * FA_D, (long)S * FA_D, FA_D);
-}
-
 extern "C" void flash_attn_fwd_strided(
     const void* q, const void* k, const void* v, void* out, void* lse,
     int B, int Hq, int Hkv, int S, float scale, int causal, int window,
@@ -364,18 +331,24 @@ extern "C" void flash_attn_fwd_strided(
       st[9], st[10], st[11]);
 }
 
+// dense (B, H, S, 128) entry points
 extern "C" void flash_attn_fwd_window(const void* q, const void* k,
                                       const void* v, void* out, void* lse,
                                       int B, int Hq, int Hkv, int S,
                                       float scale, int window,
                                       hipStream_t stream) {
-  dim3 grid(Hq, (S + FA_QBLK - 1) / FA_QBLK, B);
-  size_t lds = FA_LDS_TOTAL;
-  flash_fwd_kernel<<<grid, 512, lds, stream>>>(
-      (const short*)q, (const short*)k, (const short*)v, (short*)out,
-      (float*)lse, B, Hq, Hkv, S, scale, 1, window,
-      (long)Hq * S * FA_D, (long)S * FA_D, FA_D,
-      (long)Hkv * S * FA_D, (long)S * FA_D, FA_D,
-      (long)Hkv * S * FA_D, (long)S * FA_D, FA_D,
-      (long)Hq * S * FA_D, (long)S * FA_D, FA_D);
+  long st[12];
+  fa_dense_strides(st, Hq, Hkv, S);
+  flash_attn_fwd_strided(q, k, v, out, lse, B, Hq, Hkv, S, scale, 1, window,
+                         st, stream);
+}
+
+extern "C" void flash_attn_fwd(const void* q, const void* k, const void* v,
+                               void* out, void* lse, int B, int Hq, int Hkv,
+                               int S, float scale, int causal,
+                               hipStream_t stream) {
+  long st[12];
+  fa_dense_strides(st, Hq, Hkv, S);
+  flash_attn_fwd_strided(q, k, v, out, lse, B, Hq, Hkv, S, scale, causal, 0,
+                         st, stream);
 }

@@ -24,11 +24,7 @@
 // are per-lane scalars; operands that need the other orientation go
 // through small per-wave LDS tiles written from the accumulator layout.
 
-#include "common.h"
-#include "mfma.h"
-
-#define FA_D 128
-#define LOG2E 1.4426950408889634f
+#include "flash_common.h"
 
 // ---------------------------------------------------------------------------
 // delta = rowsum(dO * O)
@@ -61,49 +57,6 @@ fa_bwd_delta_kernel(const short* __restrict__ dout,
     for (int off = 8; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
     if (sub == 0) delta[row] = s;
   }
-}
-
-// ---------------------------------------------------------------------------
-// shared helpers for the two main kernels
-// ---------------------------------------------------------------------------
-
-// Stage a 64x128 bf16 tile ONCE, in the dual-use image of mfma.h (256-byte
-// rows, chunk XOR of img_off): the same copy feeds the ds_read_b128 row
-// reads (S^T / dP^T A fragments) and the ds_read_b64_tr_b16 transposed
-// reads (B fragments of the dV/dK/dQ mfmas).  Thread t owns NR consecutive
-// rows at 16-byte chunk t&15 (NR = 64*16 / blockDim.x), i.e. NR coalesced
-// b128 global loads and NR ds_write_b128.  Rows past the end of the
-// sequence are CLAMPED, never skipped: every image row always holds data,
-// so the transposed reads run with all lanes active (pad, don't mask).
-#define TILE64_B (64 * IMG_ROW_B)   // 16384 B
-
-template <int NR>
-struct StageRegs { uint4v v[NR]; };
-
-template <int NR>
-__device__ __forceinline__ StageRegs<NR> load_tile64(
-    const short* __restrict__ src, long src_row0, long src_stride,
-    int rows_valid) {
-  const int rp = threadIdx.x >> 4;
-  const int c16 = threadIdx.x & 15;
-  const int last = rows_valid > 0 ? rows_valid - 1 : 0;
-  StageRegs<NR> r;
-#pragma unroll
-  for (int i = 0; i < NR; ++i) {
-    int row = NR * rp + i;
-    int rr = row < rows_valid ? row : last;
-    r.v[i] = *(const uint4v*)(src + (src_row0 + rr) * src_stride + c16 * 8);
-  }
-  return r;
-}
-
-template <int NR>
-__device__ __forceinline__ void write_tile64(StageRegs<NR> r, char* img) {
-  const int rp = threadIdx.x >> 4;
-  const int c16 = threadIdx.x & 15;
-#pragma unroll
-  for (int i = 0; i < NR; ++i)
-    *(uint4v*)(img + img_off(NR * rp + i, c16)) = r.v[i];
 }
 
 // ---------------------------------------------------------------------------
@@ -147,8 +100,7 @@ fa_bwd_dkdv_kernel(const short* __restrict__ qp, const short* __restrict__ kp,
   //
   // The score/dS tiles never touch LDS: S^T/dP are computed with Q on the
   // A operand (q in accumulator REGISTER rows, kv in lanes), so the
-  // pack_bf16x2 + permlane32_swap repack from the forward kernel turns
-  // them directly into the A fragments of the dV/dK mfmas (k-dim = q,
+  // register repack (acc8_to_frag, flash_common.h) turns them directly into the A fragments of the dV/dK mfmas (k-dim = q,
   // lane = kv).  The softmax's per-q lse/delta become per-register-row
   // values read from a 128-float LDS tile staged once per q-tile.
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -304,7 +256,9 @@ fa_bwd_dkdv_kernel(const short* __restrict__ qp, const short* __restrict__ kp,
           for (int r = 0; r < 16; ++r) {
             int ql = half * 32 + acc_row(r, hi);
             int qg = q0 + ql;
-            // bitwise |: plain compares + one select, no per-element branch
+            // fa_masked<true>(my_kv, qg, ...) written out, with the window
+            // term from the kv side: the helper changes this kernel's
+            // generated code (profiles/KERNEL_NOTES.md)
             bool masked = ((causal != 0) & (my_kv > qg)) | (my_kv >= S) |
                 (qg >= S) | ((window > 0) & (qg >= my_kv + window));
             st[r] = masked ? 0.f : st[r];
@@ -314,8 +268,10 @@ fa_bwd_dkdv_kernel(const short* __restrict__ qp, const short* __restrict__ kp,
         for (int r = 0; r < 16; ++r) dpt[r] = st[r] * (dpt[r] - dlt_v[r]);
 
         // repack accumulator rows (q) into A-fragment k-dim in REGISTERS
-        // (same pack pairs + permlane32_swap as the forward kernel's P
-        // repack; lane dim = kv is already in place)
+        // (lane dim = kv is already in place).  This is acc8_to_frag
+        // (flash_common.h) written out for st and dpt: calling the helper
+        // here changes this kernel's generated code
+        // (profiles/KERNEL_NOTES.md).
         frag_u pA[2], dA[2];
 #pragma unroll
         for (int cc = 0; cc < 2; ++cc) {
@@ -587,10 +543,7 @@ fa_bwd_dq_kernel(const short* __restrict__ qp, const short* __restrict__ kp,
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           int kg = kvh0 + acc_row(r, hi);
-          // bitwise |: plain compares + one select, no per-element branch
-          bool masked = ((causal != 0) & (kg > my_q)) | (kg >= S) |
-              (my_q >= S) | ((window > 0) & (kg <= my_q - window));
-          st[r] = masked ? 0.f : st[r];
+          st[r] = fa_masked<true>(kg, my_q, S, causal, window) ? 0.f : st[r];
         }
       }
       f32x16 dst;
@@ -609,26 +562,10 @@ fa_bwd_dq_kernel(const short* __restrict__ qp, const short* __restrict__ kp,
                                         half * 32 + ck * 16, nb * 32);
 
       // repack dS accumulator rows (kv) into A-fragment k-dim in
-      // REGISTERS (lane dim q already in place) — same pack pairs +
-      // permlane32_swap as the forward P repack; no pw LDS round-trip
+      // REGISTERS (lane dim q already in place)
       frag_u dA[2];
 #pragma unroll
-      for (int cc = 0; cc < 2; ++cc) {
-        uint b0 = pack_bf16x2(dst[8 * cc + 0], dst[8 * cc + 1]);
-        uint b1 = pack_bf16x2(dst[8 * cc + 2], dst[8 * cc + 3]);
-        uint b2 = pack_bf16x2(dst[8 * cc + 4], dst[8 * cc + 5]);
-        uint b3 = pack_bf16x2(dst[8 * cc + 6], dst[8 * cc + 7]);
-        {
-          auto r01 = __builtin_amdgcn_permlane32_swap(b0, b2, false, false);
-          b0 = r01[0]; b2 = r01[1];
-        }
-        {
-          auto r23 = __builtin_amdgcn_permlane32_swap(b1, b3, false, false);
-          b1 = r23[0]; b3 = r23[1];
-        }
-        dA[cc].u[0] = b0; dA[cc].u[1] = b1;
-        dA[cc].u[2] = b2; dA[cc].u[3] = b3;
-      }
+      for (int cc = 0; cc < 2; ++cc) dA[cc] = acc8_to_frag(dst, 8 * cc);
 
       // dQ[q][d] += sum_k dS[q][k] K[k][d]
       //   A = dS (registers, lane=q), B = K[k][d] (transposed reads)
@@ -718,19 +655,10 @@ extern "C" void flash_attn_bwd(const void* q, const void* k, const void* v,
                                void* dk, void* dv, int B, int Hq, int Hkv,
                                int S, float scale, int causal,
                                hipStream_t stream) {
-  const long qd[3] = {(long)Hq * S * FA_D, (long)S * FA_D, FA_D};
-  const long kd[3] = {(long)Hkv * S * FA_D, (long)S * FA_D, FA_D};
   long st[24];
-  for (int i = 0; i < 3; ++i) {
-    st[0 + i] = qd[i];            // q
-    st[3 + i] = kd[i];            // k
-    st[6 + i] = kd[i];            // v
-    st[9 + i] = qd[i];            // out
-    st[12 + i] = qd[i];           // dout
-    st[15 + i] = qd[i];           // dq
-    st[18 + i] = qd[i];           // dk (per-Q-head buffers)
-    st[21 + i] = qd[i];           // dv
-  }
+  fa_dense_strides(st, Hq, Hkv, S);
+  // dout, dq, dk, dv are q-shaped (dk/dv are per-Q-head buffers)
+  for (int i = 12; i < 24; ++i) st[i] = st[i % 3];
   flash_attn_bwd_strided(q, k, v, out, dout, lse, delta, dq, dk, dv, B, Hq,
                          Hkv, S, scale, causal, 0, st, stream);
 }

@@ -39,12 +39,6 @@ __device__ __forceinline__ uint pack_bf16x2(float lo, float hi) {
   return r.u;
 }
 
-// XOR swizzle: spread 16B slots of a row-major LDS tile over banks
-// (cdna_hip_programming.md §6 G4: byte ^= (row&7)<<4)
-__device__ __forceinline__ int swz(int row, int byte_in_row) {
-  return byte_in_row ^ ((row & 7) << 4);
-}
-
 // ---------------------------------------------------------------------------
 // Dual-use LDS image of a [rows][128 bf16] tile (cdna_hip_programming.md
 // T10, layout (b)): plain 256-byte rows whose 16-byte chunks are XORed so
