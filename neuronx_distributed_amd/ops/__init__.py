@@ -717,3 +717,152 @@ def decode_attn_step(q2: torch.Tensor, k2: torch.Tensor, v2: torch.Tensor,
                     Smax, ctypes.c_float(scale), int(q2.stride(0)),
                     int(k2.stride(0)), _stream())
     return out
+
+
+# ---------------------------------------------------------------------------
+# Native MX linear (block-scaled MFMA; csrc/mx_gemm.hip)
+# ---------------------------------------------------------------------------
+
+_MX_FMT_CODE = {"fp8_e4m3": 0, "fp4_e2m1": 4}  # the instruction's cbsz/blgp
+
+
+def mx_gemm_available() -> bool:
+    lib = _load()
+    return lib is not None and hasattr(lib, "mx_gemm")
+
+
+def _mx_check_dense(name: str, t: torch.Tensor, dtype):
+    if not t.is_cuda:
+        raise ValueError(f"{name} must be a GPU tensor")
+    if t.dtype != dtype:
+        raise ValueError(f"{name} must be {dtype}, got {t.dtype}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous: shape "
+                         f"{tuple(t.shape)} strides {t.stride()}")
+    if t.data_ptr() % 16:
+        raise ValueError(f"{name} must be 16-byte aligned: shape "
+                         f"{tuple(t.shape)} at 0x{t.data_ptr():x}")
+
+
+def mx_quantize_rows(x: torch.Tensor):
+    """bf16 (..., K) -> (e4m3 payload uint8 (..., K), e8m0 scales uint8
+    (..., K/32)), bit-identical to ``pack_mx(*quantize_mx(x, "fp8_e4m3"))``.
+    Leading dims are flattened; a 2-D input may be a row-strided view with
+    a dense last dim."""
+    lib = _require_lib()
+    if not x.is_cuda or x.dtype != torch.bfloat16:
+        raise ValueError(f"mx_quantize_rows: x must be a bf16 GPU tensor, "
+                         f"got {x.dtype} on {x.device}")
+    K = x.shape[-1] if x.dim() else 0
+    if x.dim() < 1 or K < 32 or K % 32 or x.numel() == 0:
+        raise ValueError(f"mx_quantize_rows: K must be a positive multiple "
+                         f"of 32 and x non-empty, got {tuple(x.shape)}")
+    x2 = x if x.dim() == 2 else x.reshape(-1, K)
+    M = x2.shape[0]
+    if x2.stride(1) != 1 or (M > 1 and (x2.stride(0) < K
+                                        or x2.stride(0) % 8)):
+        raise ValueError(f"mx_quantize_rows: rows must be dense with a "
+                         f"16-byte-multiple stride: shape {tuple(x2.shape)} "
+                         f"strides {x2.stride()}")
+    if x2.data_ptr() % 16:
+        raise ValueError(f"mx_quantize_rows: x must be 16-byte aligned: "
+                         f"shape {tuple(x2.shape)} at 0x{x2.data_ptr():x}")
+    rs = x2.stride(0) if M > 1 else K
+    q = torch.empty(M, K, dtype=torch.uint8, device=x.device)
+    s = torch.empty(M, K // 32, dtype=torch.uint8, device=x.device)
+    rc = lib.mx_quantize_rows(_ptr(x2), ctypes.c_long(rs), _ptr(q), _ptr(s),
+                              M, K, _stream())
+    if rc != 0:
+        raise ValueError(f"mx_quantize_rows rejected shape {tuple(x2.shape)}"
+                         f" row stride {rs}")
+    lead = x.shape[:-1]
+    return q.reshape(*lead, K), s.reshape(*lead, K // 32)
+
+
+def _mx_check_weight(who: str, w_payload, w_scales, fmt, bias, out_dtype):
+    """Validate the weight side of the kernel contract; returns (N, K,
+    fp32 bias or None, out dtype).  Raises before anything is launched."""
+    if fmt not in _MX_FMT_CODE:
+        raise ValueError(f"{who}: weight format {fmt!r} not supported "
+                         f"(one of {tuple(_MX_FMT_CODE)})")
+    out_dtype = out_dtype or torch.bfloat16
+    if out_dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError(f"{who}: out_dtype {out_dtype} not supported")
+    _mx_check_dense(f"{who}: w_payload", w_payload, torch.uint8)
+    _mx_check_dense(f"{who}: w_scales", w_scales, torch.uint8)
+    if w_payload.dim() != 2 or w_scales.dim() != 2:
+        raise ValueError(f"{who}: payload {tuple(w_payload.shape)} / "
+                         f"scales {tuple(w_scales.shape)} must be 2-D")
+    N = w_payload.shape[0]
+    K = w_payload.shape[1] * (2 if fmt == "fp4_e2m1" else 1)
+    if K < 128 or K % 128 or N < 16 or N % 16:
+        raise ValueError(f"{who}: N={N}, K={K} outside the kernel "
+                         f"contract (K % 128 == 0, N % 16 == 0)")
+    if tuple(w_scales.shape) != (N, K // 32):
+        raise ValueError(f"{who}: scales {tuple(w_scales.shape)} do not "
+                         f"match payload (N={N}, K={K})")
+    bias32 = None
+    if bias is not None:
+        if bias.numel() != N or not bias.is_cuda:
+            raise ValueError(f"{who}: bias {tuple(bias.shape)} does not "
+                             f"match N={N}")
+        bias32 = bias.detach().reshape(N).float().contiguous()
+        _mx_check_dense(f"{who}: bias", bias32, torch.float32)
+    return N, K, bias32, out_dtype
+
+
+def _mx_gemm_launch(lib, a_payload, a_scales, w_payload, w_scales, fmt,
+                    bias32, out_dtype, M, N, K):
+    out = torch.empty(M, N, dtype=out_dtype, device=a_payload.device)
+    rc = lib.mx_gemm(_ptr(a_payload), _ptr(a_scales), _ptr(w_payload),
+                     _ptr(w_scales),
+                     _ptr(bias32) if bias32 is not None else None,
+                     _ptr(out), M, N, K, _MX_FMT_CODE[fmt],
+                     1 if out_dtype == torch.float32 else 0, _stream())
+    if rc != 0:
+        raise ValueError(f"mx_gemm rejected M={M}, N={N}, K={K}, {fmt}")
+    return out
+
+
+def mx_gemm_packed(a_payload: torch.Tensor, a_scales: torch.Tensor,
+                   w_payload: torch.Tensor, w_scales: torch.Tensor, fmt: str,
+                   bias=None, out_dtype=None):
+    """C = A_mx . W_mx^T on the block-scaled MFMA for an already-quantized
+    MXFP8 activation: payload (M, K) + scales (M, K/32), both uint8.  Same
+    weight contract and checks as :func:`mx_linear`."""
+    lib = _require_lib()
+    who = "mx_gemm_packed"
+    N, K, bias32, out_dtype = _mx_check_weight(who, w_payload, w_scales, fmt,
+                                               bias, out_dtype)
+    _mx_check_dense(f"{who}: a_payload", a_payload, torch.uint8)
+    _mx_check_dense(f"{who}: a_scales", a_scales, torch.uint8)
+    M = a_payload.shape[0] if a_payload.dim() == 2 else 0
+    if M < 1 or tuple(a_payload.shape) != (M, K) or \
+            tuple(a_scales.shape) != (M, K // 32):
+        raise ValueError(f"{who}: activation payload "
+                         f"{tuple(a_payload.shape)} / scales "
+                         f"{tuple(a_scales.shape)} do not match K={K}")
+    return _mx_gemm_launch(lib, a_payload, a_scales, w_payload, w_scales,
+                           fmt, bias32, out_dtype, M, N, K)
+
+
+def mx_linear(x: torch.Tensor, w_payload: torch.Tensor,
+              w_scales: torch.Tensor, fmt: str, bias=None, out_dtype=None):
+    """y = x . W^T on the block-scaled MFMA: x bf16 (..., K) is quantized to
+    MXFP8 by ``mx_quantize_rows``; W is an MX payload (N, K) e4m3 or
+    (N, K/2) e2m1 with e8m0 scales (N, K/32) (microscaling.pack_mx).
+    Contract: K % 128 == 0, N % 16 == 0; anything else raises ValueError
+    and launches nothing.  out_dtype: bf16 (default) or fp32; the bias is
+    added in fp32 before the output rounding."""
+    lib = _require_lib()
+    N, K, bias32, out_dtype = _mx_check_weight("mx_linear", w_payload,
+                                               w_scales, fmt, bias, out_dtype)
+    if x.dim() < 1 or x.shape[-1] != K or x.numel() == 0:
+        raise ValueError(f"mx_linear: x {tuple(x.shape)} does not match "
+                         f"K={K}")
+    xq, xs = mx_quantize_rows(x)
+    M = xq.numel() // K
+    out = _mx_gemm_launch(lib, xq.reshape(M, K), xs.reshape(M, K // 32),
+                          w_payload, w_scales, fmt, bias32, out_dtype, M, N,
+                          K)
+    return out.reshape(*x.shape[:-1], N)

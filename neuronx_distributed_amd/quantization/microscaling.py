@@ -68,3 +68,105 @@ def mx_matmul(a: torch.Tensor, qb: torch.Tensor, b_scales: torch.Tensor,
               dtype=torch.bfloat16) -> torch.Tensor:
     """a (bf16) @ dequant(qb) — emulation of the scaled-MFMA GEMM."""
     return a.to(dtype) @ dequantize_mx(qb, b_scales, axis=-2, dtype=dtype)
+
+
+# ---------------------------------------------------------------------------
+# Stored MX format + the MX linear (native kernel: ops/csrc/mx_gemm.hip)
+#
+# Public layout contract (what checkpoints and the HIP kernel share):
+#   fp8_e4m3 payload  uint8 (..., K)    one e4m3fn byte per element
+#   fp4_e2m1 payload  uint8 (..., K/2)  element 2i in the LOW nibble, 2i+1 in
+#                                       the high nibble; nibble = sign<<3 |
+#                                       index into _FP4_GRID
+#   scales            uint8 (..., K/32) biased e8m0: byte = scale + 127
+#                                       (0..254; 255 never occurs)
+# Supported natively: fp8_e4m3 activations x {fp8_e4m3, fp4_e2m1} weights,
+# forward only.  fp6 / e5m2, backward and grouped (MoE) MX GEMMs are out of
+# scope; mx_matmul and moe.blockwise_mm_mx keep their emulation.
+# ---------------------------------------------------------------------------
+
+MX_NATIVE_FORMATS = ("fp8_e4m3", "fp4_e2m1")
+MX_GEMM_K = 128   # native kernel contract: K % 128 == 0, N % 16 == 0
+MX_GEMM_N = 16
+
+
+def _check_native_fmt(fmt: str):
+    if fmt not in MX_NATIVE_FORMATS:
+        raise ValueError(f"MX storage format {fmt!r} not supported "
+                         f"(one of {MX_NATIVE_FORMATS})")
+
+
+def pack_mx(q: torch.Tensor, scales: torch.Tensor, fmt: str
+            ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(q, scales) of ``quantize_mx(..., axis=-1)`` -> (payload, scales) in
+    the stored uint8 layout above."""
+    _check_native_fmt(fmt)
+    if fmt == "fp8_e4m3":
+        payload = q.to(torch.float8_e4m3fn).view(torch.uint8)
+    else:
+        if q.shape[-1] % 2:
+            raise ValueError(f"fp4 payload needs an even K, got {q.shape}")
+        idx = torch.bucketize(q.abs().float(), _FP4_GRID.to(q.device))
+        code = (idx | (torch.signbit(q).to(idx.dtype) << 3)).to(torch.uint8)
+        payload = code[..., 0::2] | (code[..., 1::2] << 4)
+    return payload.contiguous(), (scales + 127).to(torch.uint8)
+
+
+def unpack_mx(payload: torch.Tensor, scales: torch.Tensor, fmt: str
+              ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Inverse of :func:`pack_mx`: bit-identical (q, scales) in the
+    emulation dtype (fp32)."""
+    _check_native_fmt(fmt)
+    if fmt == "fp8_e4m3":
+        q = payload.view(torch.float8_e4m3fn).float()
+    else:
+        code = torch.stack([payload & 0xF, payload >> 4], dim=-1)
+        code = code.reshape(*payload.shape[:-1], payload.shape[-1] * 2)
+        mag = _FP4_GRID.to(payload.device)[(code & 7).long()]
+        q = torch.where((code & 8) != 0, -mag, mag)
+    return q, scales.float() - 127.0
+
+
+def mx_payload_k(payload: torch.Tensor, fmt: str) -> int:
+    return payload.shape[-1] * (2 if fmt == "fp4_e2m1" else 1)
+
+
+def mx_linear_emulated(x: torch.Tensor, w_payload: torch.Tensor,
+                       w_scales: torch.Tensor, fmt: str, bias=None,
+                       out_dtype=None) -> torch.Tensor:
+    """Reference MX linear: x is quantized to MXFP8 per 32-block, both
+    operands are dequantized to fp32, multiplied, and cast."""
+    wq, ws = unpack_mx(w_payload, w_scales, fmt)
+    xq, xs = quantize_mx(x, "fp8_e4m3")
+    y = dequantize_mx(xq, xs, dtype=torch.float32) @ \
+        dequantize_mx(wq, ws, dtype=torch.float32).t()
+    if bias is not None:
+        y = y + bias.float()
+    return y.to(out_dtype or x.dtype)
+
+
+def mx_native_shape_ok(x: torch.Tensor, w_payload: torch.Tensor,
+                       fmt: str) -> bool:
+    """Inside the HIP kernel's contract (bf16 x, K % 128, N % 16)?"""
+    K = x.shape[-1]
+    return (x.dtype == torch.bfloat16 and x.numel() > 0
+            and K % MX_GEMM_K == 0 and w_payload.shape[0] % MX_GEMM_N == 0)
+
+
+def mx_linear(x: torch.Tensor, w_payload: torch.Tensor,
+              w_scales: torch.Tensor, fmt: str, bias=None) -> torch.Tensor:
+    """y = x . W^T with W stored in MX format (``pack_mx``) and x quantized
+    to MXFP8 on the fly.  Inference only.
+
+    GPU tensors inside the kernel contract run the native block-scaled MFMA
+    GEMM (a missing library raises); CPU tensors and shapes outside the
+    contract run :func:`mx_linear_emulated`, the numerical reference."""
+    _check_native_fmt(fmt)
+    if w_payload.dim() != 2 or mx_payload_k(w_payload, fmt) != x.shape[-1]:
+        raise ValueError(f"mx_linear: x {tuple(x.shape)} does not match "
+                         f"{fmt} payload {tuple(w_payload.shape)}")
+    if x.is_cuda and mx_native_shape_ok(x, w_payload, fmt):
+        from .. import ops
+
+        return ops.mx_linear(x, w_payload, w_scales, fmt, bias=bias)
+    return mx_linear_emulated(x, w_payload, w_scales, fmt, bias=bias)
