@@ -133,7 +133,7 @@ class GPT2LMHeadModel(nn.Module):
         self.ln_f = LayerNorm(cfg.hidden_size, eps=cfg.layer_norm_epsilon)
         self.lm_head = ColumnParallelLinear(
             cfg.hidden_size, cfg.vocab_size, bias=False, gather_output=False,
-            init_method=_init(cfg.initializer_range))
+            dgrad_shadow=False, init_method=_init(cfg.initializer_range))
 
     def forward(self, input_ids, labels=None, pos_offset=0, kv_caches=None):
         B, S = input_ids.shape

@@ -172,7 +172,7 @@ class GPTNeoXForCausalLM(nn.Module):
                                           eps=cfg.layer_norm_epsilon)
         self.embed_out = ColumnParallelLinear(
             cfg.hidden_size, cfg.vocab_size, bias=False, gather_output=False,
-            init_method=_init(cfg.initializer_range))
+            dgrad_shadow=False, init_method=_init(cfg.initializer_range))
         cos, sin = ops.precompute_rope_freqs(
             cfg.max_position_embeddings,
             max(2, 2 * (int(cfg.head_dim * cfg.rotary_pct) // 2)),

@@ -489,7 +489,7 @@ class LlamaForCausalLM(nn.Module):
         self.model = LlamaModel(config)
         self.lm_head = ColumnParallelLinear(
             config.hidden_size, config.vocab_size, bias=False,
-            gather_output=False,
+            gather_output=False, dgrad_shadow=False,
             init_method=_init_method(config.initializer_range))
         if config.tie_word_embeddings:
             self.lm_head.weight = self.model.embed_tokens.weight

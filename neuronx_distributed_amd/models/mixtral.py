@@ -256,7 +256,7 @@ class MixtralForCausalLM(nn.Module):
         self.model = MixtralModel(config)
         self.lm_head = ColumnParallelLinear(
             config.hidden_size, config.vocab_size, bias=False,
-            gather_output=False,
+            gather_output=False, dgrad_shadow=False,
             init_method=_init_method(config.initializer_range))
         if config.tie_word_embeddings:
             self.lm_head.weight = self.model.embed_tokens.weight

@@ -564,6 +564,101 @@ def adamw_step(master: torch.Tensor, m: torch.Tensor, v: torch.Tensor,
 
 
 # ---------------------------------------------------------------------------
+# bf16 2-D transpose (csrc/transpose.hip)
+# ---------------------------------------------------------------------------
+
+def transpose_available() -> bool:
+    lib = _load()
+    return lib is not None and hasattr(lib, "transpose_bf16")
+
+
+def _transpose_tiles(lib, who: str, x: torch.Tensor, out: torch.Tensor):
+    """Validate one (source, destination) pair against the kernel contract;
+    returns its tile count.  Raises before anything is launched."""
+    if x.dim() != 2 or x.dtype != torch.bfloat16 or not x.is_cuda:
+        raise ValueError(f"{who}: source must be a 2-D bf16 GPU tensor, got "
+                         f"{tuple(x.shape)} {x.dtype} on {x.device}")
+    R, C = x.shape
+    rs = x.stride(0) if R > 1 else max(C, 8)
+    if x.stride(1) != 1 and C > 1:
+        raise ValueError(f"{who}: source rows must be dense, strides "
+                         f"{x.stride()}")
+    if out.dtype != x.dtype or out.device != x.device or \
+            tuple(out.shape) != (C, R) or not out.is_contiguous():
+        raise ValueError(f"{who}: destination must be a contiguous "
+                         f"{(C, R)} bf16 tensor on {x.device}, got "
+                         f"{tuple(out.shape)} strides {out.stride()}")
+    lib.transpose_bf16_tiles.restype = ctypes.c_long
+    tiles = lib.transpose_bf16_tiles(ctypes.c_long(R), ctypes.c_long(C),
+                                     ctypes.c_long(rs))
+    if tiles < 0 or x.data_ptr() % 16 or out.data_ptr() % 16:
+        raise ValueError(f"{who}: shape {(R, C)} row stride {rs} outside the "
+                         f"kernel contract (R, C, stride multiples of 8, "
+                         f"16-byte aligned)")
+    return tiles, rs
+
+
+def transpose(x: torch.Tensor, out: Optional[torch.Tensor] = None):
+    """x (R, C) -> (C, R) contiguous.  bf16 GPU tensors go through the tiled
+    LDS kernel: rows may be strided (a column slice of a wider buffer), R, C
+    and the row stride are multiples of 8.  ``out`` reuses a destination.
+    Anything on the CPU is the composed torch transpose."""
+    if x.dim() != 2:
+        raise ValueError(f"transpose: 2-D input expected, got {tuple(x.shape)}")
+    if out is None:
+        out = torch.empty(x.shape[1], x.shape[0], dtype=x.dtype,
+                          device=x.device)
+    if not x.is_cuda:
+        out.copy_(x.t())
+        return out
+    lib = _require_lib()
+    _, rs = _transpose_tiles(lib, "transpose", x, out)
+    rc = lib.transpose_bf16(_ptr(x), _ptr(out), ctypes.c_long(rs),
+                            ctypes.c_long(x.shape[0]),
+                            ctypes.c_long(x.shape[1]), _stream())
+    if rc != 0:
+        raise ValueError(f"transpose rejected shape {tuple(x.shape)}")
+    return out
+
+
+def transpose_batched(xs, outs=None):
+    """Transpose many 2-D matrices (different shapes allowed) in ONE launch
+    driven by a device descriptor table; same contract per matrix as
+    :func:`transpose`.  Returns the list of (C, R) results."""
+    xs = list(xs)
+    if outs is None:
+        outs = [torch.empty(x.shape[1], x.shape[0], dtype=x.dtype,
+                            device=x.device) for x in xs]
+    outs = list(outs)
+    if len(outs) != len(xs):
+        raise ValueError("transpose_batched: one destination per source")
+    if not xs:
+        return outs
+    if not xs[0].is_cuda:
+        for x, o in zip(xs, outs):
+            transpose(x, o)
+        return outs
+    lib = _require_lib()
+    rows, first = [], 0
+    for x, o in zip(xs, outs):
+        if x.device != xs[0].device:
+            raise ValueError("transpose_batched: all sources on one device")
+        tiles, rs = _transpose_tiles(lib, "transpose_batched", x, o)
+        rows.append([x.data_ptr(), o.data_ptr(), rs, x.shape[0], x.shape[1],
+                     first])
+        first += tiles
+    desc = torch.tensor(rows, dtype=torch.int64).to(xs[0].device)
+    rc = lib.transpose_bf16_batched(_ptr(desc), len(rows),
+                                    ctypes.c_long(first), _stream())
+    if rc != 0:
+        raise ValueError(f"transpose_batched rejected {len(rows)} matrices, "
+                         f"{first} tiles")
+    # desc was allocated on the launch's own stream, so the caching
+    # allocator cannot hand it out again before the kernel has read it
+    return outs
+
+
+# ---------------------------------------------------------------------------
 # Fused MoE decode (K9 parity; csrc/moe_decode.hip)
 # ---------------------------------------------------------------------------
 

@@ -32,6 +32,7 @@ import torch
 import torch.distributed as dist
 
 from ..parallel import comm, parallel_state as ps
+from ..parallel.layers import bump_weight_generation
 from ..parallel.utils import param_is_tensor_parallel, param_is_expert_parallel
 from ..utils.logger import get_logger
 
@@ -291,6 +292,10 @@ class NeuronZero1Optimizer(torch.optim.Optimizer):
 
     @torch.no_grad()
     def _all_gather_params(self, copy_master: bool = True):
+        # every path that rewrites the parameters ends here (step, fused
+        # step, load_state_dict, DCP restore), and all of them write
+        # flat_param behind the parameters' own _version counters
+        bump_weight_generation()
         works = []
         for b in self.buckets:
             shard = b.flat_param[b.shard_lo:b.shard_hi]

@@ -188,7 +188,7 @@ class _RPLOverlappedLinearRS(torch.autograd.Function):
         input_parallel, weight = ctx.saved_tensors
         tp_info = ps.get_group_info("tp")
         g = comm.all_gather(grad_output.contiguous(), dim=0, group=tp_info)
-        grad_input = g.matmul(weight)
+        grad_input = _dgrad(g, weight)
         go2d = g.reshape(-1, g.shape[-1])
         in2d = input_parallel.reshape(-1, input_parallel.shape[-1])
         grad_weight = go2d.t().matmul(in2d)
@@ -211,14 +211,41 @@ def _fp8_eligible(x: torch.Tensor, w: torch.Tensor) -> bool:
             and x.numel() // x.shape[-1] >= 2048)
 
 
+# Generation of the parameter VALUES, for caches of tensors derived from a
+# weight (fp8 quantization, the fused inference QKV weight).
+# ``weight._version`` alone misses the fused optimizer, which updates
+# ``flat_param`` through raw pointers: NeuronZero1Optimizer bumps the
+# generation in ``_all_gather_params``, the one place where it leaves the
+# parameters final (step, load_state_dict, DCP restore).  A write through
+# ``weight.data`` moves neither counter (``.data`` is an alias with a
+# version counter of its own): code that edits weights that way and relies on
+# such a cache calls ``bump_weight_generation()``.
+_WEIGHT_GENERATION = [0]
+
+
+def bump_weight_generation() -> int:
+    """Invalidate every cached tensor derived from a weight."""
+    _WEIGHT_GENERATION[0] += 1
+    return _WEIGHT_GENERATION[0]
+
+
+def weight_generation() -> int:
+    return _WEIGHT_GENERATION[0]
+
+
+def _weight_cache_key(weight: torch.Tensor):
+    return (weight.data_ptr(), weight._version, _WEIGHT_GENERATION[0])
+
+
 def _fp8_quantized_weight(weight: torch.Tensor):
-    """Per-channel e4m3 weight quantization, cached per weight VERSION so
-    the n_micro forward calls of one optimizer step quantize once."""
+    """Per-channel e4m3 weight quantization, cached per weight VERSION and
+    value generation so the n_micro forward calls of one optimizer step
+    quantize once."""
     from ..quantization.quantization_config import (QuantizationConfig,
                                                     QuantizedDtype)
     from ..quantization.quantization_utils import quantize_symmetric
 
-    key = (weight.data_ptr(), weight._version)
+    key = _weight_cache_key(weight)
     cache = getattr(weight, "_fp8_cache", None)
     if cache is None or cache[0] != key:
         cfg = QuantizationConfig(quantized_dtype=QuantizedDtype.F8E4M3,
@@ -248,6 +275,59 @@ def _forward_gemm(total_input: torch.Tensor, weight: torch.Tensor, bias):
             out = out + bias
         return out
     return F.linear(total_input, weight, bias)
+
+
+def _dgrad_shadow_enabled() -> bool:
+    return os.environ.get("NXDA_DGRAD_SHADOW", "1") == "1"
+
+
+# The transposes cost ~0.1 ms per 4096x4096 weight per backward against a
+# GEMM of ~1 ms: below this size the dgrad stays on the strided weight.
+_DGRAD_SHADOW_MIN_NUMEL = 4096 * 4096
+
+
+def _dgrad_shadow_eligible(weight: torch.Tensor) -> bool:
+    """Weights whose dgrad runs on W^T: the big GEMMs only (out*in >=
+    4096x4096), shapes inside the transpose kernel's contract; a weight opts
+    out with ``weight.dgrad_shadow = False`` (the vocabulary projections)."""
+    return (weight.dim() == 2 and weight.dtype == torch.bfloat16
+            and weight.is_contiguous()
+            and weight.numel() >= _DGRAD_SHADOW_MIN_NUMEL
+            and weight.shape[0] % 8 == 0 and weight.shape[1] % 8 == 0
+            and getattr(weight, "dgrad_shadow", True))
+
+
+def dgrad_weight_t(weight: torch.Tensor) -> Optional[torch.Tensor]:
+    """W^T (in, out) contiguous for the dgrad of ``y = x W^T``, or None when
+    the weight keeps the strided form.
+
+    ``dY @ W`` walks W along its strided dimension (hipBLASLt NN class);
+    ``F.linear(dY, W^T)`` is the same product with both operands contiguous
+    along the contraction (TN class, the forward's), and the library stops
+    re-staging W through LDS in every tile.
+
+    W^T is built by ``ops.transpose`` from the weight AS IT IS at this
+    backward and dropped after it: nothing is cached, so no write to the
+    weight (optimizer kernels on raw pointers, ``weight.data.mul_()``, which
+    no version counter sees) can leave a stale copy behind, and nothing is
+    attached to the parameter or reaches a checkpoint.  The price is one
+    transpose per weight per microbatch (~0.4 % of the Llama-2-7B step, an
+    eighth of what the TN product saves; profiles/README.md)."""
+    if torch.is_grad_enabled():  # double backward differentiates through W
+        return None
+    if not (_dgrad_shadow_enabled() and _dgrad_shadow_eligible(weight)):
+        return None
+    from .. import ops as _ops
+
+    return _ops.transpose(weight.detach())
+
+
+def _dgrad(grad_output: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
+    """grad_input = grad_output @ W, as a K-contiguous product if eligible."""
+    w_t = dgrad_weight_t(weight)
+    if w_t is None:
+        return grad_output.matmul(weight)
+    return F.linear(grad_output, w_t)
 
 
 class LinearWithAsyncCommunication(torch.autograd.Function):
@@ -302,7 +382,7 @@ class LinearWithAsyncCommunication(torch.autograd.Function):
         handle = None
 
         grad_output = grad_output.contiguous()
-        grad_input = grad_output.matmul(weight)
+        grad_input = _dgrad(grad_output, weight)
 
         if ctx.sequence_parallel_enabled and ctx.compute_weight_gradient:
             # re-gather the saved sharded input for the weight-grad GEMM
@@ -413,11 +493,14 @@ class ColumnParallelLinear(BaseParallelLinear):
     def __init__(self, input_size, output_size, bias=True, gather_output=True,
                  dtype=None, device=None, init_method=None, stride=1,
                  sequence_parallel_enabled=False, keep_master_weight=False,
-                 skip_bias_add=False):
+                 skip_bias_add=False, dgrad_shadow=True):
         super().__init__()
         self.input_size = input_size
         self.output_size = output_size
         self.gather_output = gather_output
+        # False: the dgrad stays on the strided weight (vocabulary
+        # projections: no gain at 32000x4096, profiles/README.md)
+        self.dgrad_shadow = dgrad_shadow
         self.sequence_parallel_enabled = sequence_parallel_enabled
         self.skip_bias_add = skip_bias_add
         self.stride = stride
@@ -457,6 +540,10 @@ class ColumnParallelLinear(BaseParallelLinear):
             input_parallel = copy_to_tensor_model_parallel_region(input_)
 
         bias = self.bias if not self.skip_bias_add else None
+        if not self.dgrad_shadow:
+            # marked here, not at construction: weight tying replaces the
+            # Parameter object after __init__
+            self.weight.dgrad_shadow = False
         output_parallel = linear_with_async_allreduce(
             input_parallel, self.weight, bias,
             async_grad_allreduce=self.async_tensor_model_parallel_allreduce,

@@ -23,7 +23,8 @@ import torch.distributed as dist
 
 from . import comm
 from . import parallel_state as ps
-from .layers import BaseParallelLinear, default_init_method
+from .layers import (BaseParallelLinear, default_init_method, _dgrad,
+                     _weight_cache_key, dgrad_weight_t)
 from .utils import divide, set_tensor_model_parallel_attributes
 
 
@@ -108,9 +109,16 @@ class _QKVLinearWithAsyncCommunication(torch.autograd.Function):
         gq = gq.contiguous()
         gk = gk.contiguous()
         gv = gv.contiguous()
-        grad_input = gq.matmul(wq)
-        grad_input += gk.matmul(wk)
-        grad_input += gv.matmul(wv)
+        grad_input = _dgrad(gq, wq)
+        for g, w in ((gk, wk), (gv, wv)):
+            w_t = dgrad_weight_t(w)
+            if w_t is None:
+                grad_input += g.matmul(w)
+            else:
+                # accumulate inside the GEMM (beta = 1): no activation-sized
+                # add pass, and the sum is rounded to bf16 once
+                gi2d = grad_input.view(-1, grad_input.shape[-1])
+                torch.addmm(gi2d, g.view(-1, g.shape[-1]), w_t.t(), out=gi2d)
 
         handle = None
         if ctx.sequence_parallel:
@@ -286,11 +294,12 @@ class GQAQKVColumnParallelLinear(BaseParallelLinear):
 
     def _fused_qkv_weight(self):
         """Concatenated [q;k;v] weight for the single-GEMM inference path,
-        cached and invalidated on in-place weight updates (``_version``) or
-        re-assignment (``data_ptr``).  Decode steps otherwise pay 3
+        cached and invalidated on in-place weight updates (``_version``),
+        re-assignment (``data_ptr``) or an optimizer step that writes the
+        flat buffer behind both (``layers._weight_cache_key``).  Decode steps otherwise pay 3
         latency-bound skinny GEMM launches per layer (measured 45 us vs 18
         us fused at B=32, llama3-8b shapes)."""
-        key = tuple((w._version, w.data_ptr())
+        key = tuple(_weight_cache_key(w)
                     for w in (self.weight_q, self.weight_k, self.weight_v))
         cached = getattr(self, "_qkv_cat_cache", None)
         if cached is None or cached[0] != key:

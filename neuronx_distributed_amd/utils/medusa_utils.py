@@ -66,7 +66,7 @@ class MedusaHead(torch.nn.Module):
         self.act = torch.nn.SiLU()
         self.lm_head = ColumnParallelLinear(hidden_size, vocab_size,
                                             bias=False, gather_output=False,
-                                            dtype=dtype)
+                                            dtype=dtype, dgrad_shadow=False)
 
     def forward(self, hidden):
         return self.lm_head(hidden + self.act(self.proj(hidden)))
