@@ -941,11 +941,135 @@ def mx_gemm_packed(a_payload: torch.Tensor, a_scales: torch.Tensor,
                            fmt, bias32, out_dtype, M, N, K)
 
 
+def mx_skinny_available() -> bool:
+    lib = _load()
+    return lib is not None and hasattr(lib, "mx_skinny_gemm")
+
+
+MX_SKINNY_MAX_M = 32     # csrc/mx_skinny.hip: two 16-row x fragments
+_MX_SKINNY_CUS = 256     # workgroups that fill an MI355X once
+
+
+def _mx_skinny_tile_n(M: int) -> int:
+    """n rows per workgroup of mx_skinny.hip: one 16-row W fragment per x
+    fragment."""
+    return 16 if M <= 16 else 32
+
+
+def mx_skinny_splits(M: int, N: int, K: int, fmt: str) -> int:
+    """Global K-split count of the skinny MX GEMM, in [1, K // 128].
+
+    The four waves of a workgroup already split K among themselves, so a
+    global split is added only while the N / tile workgroups leave CUs idle:
+    1 when they already give one workgroup per CU, else the smallest count
+    that does, capped so every wave of every slice keeps at least one
+    128-deep K step (K // 512).  The same rule holds for both formats: the
+    partials cost (KS, M, N) fp32 of traffic whatever the weight format."""
+    if fmt not in _MX_FMT_CODE:
+        raise ValueError(f"mx_skinny_splits: weight format {fmt!r} not "
+                         f"supported (one of {tuple(_MX_FMT_CODE)})")
+    if not 1 <= M <= MX_SKINNY_MAX_M or N < 16 or N % 16 or K < 128 \
+            or K % 128:
+        raise ValueError(f"mx_skinny_splits: M={M}, N={N}, K={K} outside "
+                         f"the kernel contract (M <= {MX_SKINNY_MAX_M}, "
+                         f"K % 128 == 0, N % 16 == 0)")
+    tile = _mx_skinny_tile_n(M)
+    groups = -(-N // tile)
+    if groups >= _MX_SKINNY_CUS:
+        return 1
+    want = -(-_MX_SKINNY_CUS // groups)
+    return max(1, min(want, K // 512, K // 128))
+
+
+def _mx_skinny_enabled() -> bool:
+    """NXDA_MX_SKINNY=0 (read per call) turns the skinny dispatch off;
+    unset or any other value leaves it on."""
+    return os.environ.get("NXDA_MX_SKINNY", "1").strip() != "0"
+
+
+def _mx_skinny_gate(x: torch.Tensor, M: int, N: int, K: int, fmt: str
+                    ) -> bool:
+    """The one place that decides whether ``mx_linear`` takes the skinny
+    kernel instead of quantize + the 128x128 tile."""
+    return (_mx_skinny_enabled() and x.is_cuda
+            and 1 <= M <= MX_SKINNY_MAX_M and mx_skinny_available())
+
+
+def _mx_check_x(who: str, x: torch.Tensor, K: int):
+    """The x checks of mx_quantize_rows; returns (2-D view, M, row stride)."""
+    if not x.is_cuda or x.dtype != torch.bfloat16:
+        raise ValueError(f"{who}: x must be a bf16 GPU tensor, got "
+                         f"{x.dtype} on {x.device}")
+    if x.dim() < 1 or x.shape[-1] != K or x.numel() == 0:
+        raise ValueError(f"{who}: x {tuple(x.shape)} does not match K={K}")
+    x2 = x if x.dim() == 2 else x.reshape(-1, K)
+    M = x2.shape[0]
+    if x2.stride(1) != 1 or (M > 1 and (x2.stride(0) < K
+                                        or x2.stride(0) % 8)):
+        raise ValueError(f"{who}: rows must be dense with a "
+                         f"16-byte-multiple stride: shape {tuple(x2.shape)} "
+                         f"strides {x2.stride()}")
+    if x2.data_ptr() % 16:
+        raise ValueError(f"{who}: x must be 16-byte aligned: shape "
+                         f"{tuple(x2.shape)} at 0x{x2.data_ptr():x}")
+    return x2, M, (x2.stride(0) if M > 1 else K)
+
+
+def _mx_skinny_launch(lib, x2, rs, w_payload, w_scales, fmt, bias32,
+                      out_dtype, M, N, K, k_splits):
+    KS = min(int(k_splits), K // 128)
+    out = torch.empty(M, N, dtype=out_dtype, device=x2.device)
+    # cached-alloc tensor with a static shape: hipGraph-capturable
+    ws = (torch.empty(KS, M, N, dtype=torch.float32, device=x2.device)
+          if KS > 1 else None)
+    rc = lib.mx_skinny_gemm(_ptr(x2), ctypes.c_long(rs), _ptr(w_payload),
+                            _ptr(w_scales),
+                            _ptr(bias32) if bias32 is not None else None,
+                            _ptr(out), _ptr(ws) if ws is not None else None,
+                            M, N, K, _MX_FMT_CODE[fmt],
+                            1 if out_dtype == torch.float32 else 0, KS,
+                            _stream())
+    if rc != 0:
+        raise ValueError(f"mx_skinny_gemm rejected M={M}, N={N}, K={K}, "
+                         f"{fmt}, k_splits={KS}")
+    return out
+
+
+def mx_linear_skinny(x: torch.Tensor, w_payload: torch.Tensor,
+                     w_scales: torch.Tensor, fmt: str, bias=None,
+                     out_dtype=None, k_splits=None):
+    """:func:`mx_linear` for at most 32 rows of x (decode) in one fused
+    kernel: x is quantized to MXFP8 inside the GEMM (same bytes as
+    ``mx_quantize_rows``) and W is streamed once.  Same weight contract as
+    ``mx_linear`` and the x contract of ``mx_quantize_rows``, plus M <= 32;
+    anything else raises ValueError and launches nothing.  ``k_splits``:
+    global K-split count (clamped to K // 128); default
+    :func:`mx_skinny_splits`."""
+    lib = _require_lib()
+    who = "mx_linear_skinny"
+    N, K, bias32, out_dtype = _mx_check_weight(who, w_payload, w_scales, fmt,
+                                               bias, out_dtype)
+    x2, M, rs = _mx_check_x(who, x, K)
+    if M > MX_SKINNY_MAX_M:
+        raise ValueError(f"{who}: M={M} rows, at most {MX_SKINNY_MAX_M}")
+    if k_splits is None:
+        k_splits = mx_skinny_splits(M, N, K, fmt)
+    elif int(k_splits) < 1:
+        raise ValueError(f"{who}: k_splits={k_splits} must be >= 1")
+    if not mx_skinny_available():
+        raise RuntimeError("nxd_ops library has no mx_skinny_gemm — rebuild")
+    out = _mx_skinny_launch(lib, x2, rs, w_payload, w_scales, fmt, bias32,
+                            out_dtype, M, N, K, k_splits)
+    return out.reshape(*x.shape[:-1], N)
+
+
 def mx_linear(x: torch.Tensor, w_payload: torch.Tensor,
               w_scales: torch.Tensor, fmt: str, bias=None, out_dtype=None):
     """y = x . W^T on the block-scaled MFMA: x bf16 (..., K) is quantized to
-    MXFP8 by ``mx_quantize_rows``; W is an MX payload (N, K) e4m3 or
-    (N, K/2) e2m1 with e8m0 scales (N, K/32) (microscaling.pack_mx).
+    MXFP8; W is an MX payload (N, K) e4m3 or (N, K/2) e2m1 with e8m0 scales
+    (N, K/32) (microscaling.pack_mx).  Up to 32 rows of x (decode) take the
+    fused skinny kernel (:func:`mx_linear_skinny`; ``NXDA_MX_SKINNY=0``
+    turns that off), more rows ``mx_quantize_rows`` + the 128x128 tile.
     Contract: K % 128 == 0, N % 16 == 0; anything else raises ValueError
     and launches nothing.  out_dtype: bf16 (default) or fp32; the bias is
     added in fp32 before the output rounding."""
@@ -955,6 +1079,12 @@ def mx_linear(x: torch.Tensor, w_payload: torch.Tensor,
     if x.dim() < 1 or x.shape[-1] != K or x.numel() == 0:
         raise ValueError(f"mx_linear: x {tuple(x.shape)} does not match "
                          f"K={K}")
+    if _mx_skinny_gate(x, x.numel() // K, N, K, fmt):
+        x2, M, rs = _mx_check_x("mx_linear", x, K)
+        out = _mx_skinny_launch(lib, x2, rs, w_payload, w_scales, fmt,
+                                bias32, out_dtype, M, N, K,
+                                mx_skinny_splits(M, N, K, fmt))
+        return out.reshape(*x.shape[:-1], N)
     xq, xs = mx_quantize_rows(x)
     M = xq.numel() // K
     out = _mx_gemm_launch(lib, xq.reshape(M, K), xs.reshape(M, K // 32),

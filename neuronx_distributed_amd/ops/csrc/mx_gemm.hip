@@ -19,8 +19,15 @@
 //
 // Ragged tiles: rows past M (N) are loaded from the clamped last row and
 // their results are never stored.  K % 128 == 0, N % 16 == 0, M >= 1.
+//
+// This 128x128 tile is the prefill configuration.  At M <= 32 three quarters
+// of its x tile is padding and N/128 workgroups do not fill the machine:
+// decode goes through mx_skinny.hip (M-skinny, split-K, the activation
+// quantized inside the GEMM), which ops.mx_linear dispatches to.  The
+// quantizer itself is shared with it through mx_quant.h.
 
 #include "mx_mfma.h"
+#include "mx_quant.h"
 
 #define MXG_BM 128
 #define MXG_BN 128
@@ -52,35 +59,20 @@ mx_quantize_rows_kernel(const short* __restrict__ x, long row_stride,
 #pragma unroll
   for (int i = 0; i < 4; ++i) v[i] = src[i];
 
-  // block amax on the bf16 magnitude bits (ordered like the values)
+  // the quantizer proper lives in mx_quant.h (shared with mx_skinny.hip)
   int ab = 0;
 #pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) ab = max(ab, (int)v[i][j] & 0x7FFF);
-  ab = max(ab, 0x0080);  // clamp to 2^-126 (zero / subnormal block)
-  // smallest e with amax * 2^-e <= 448 = 1.75 * 2^8, amax = 1.m * 2^E
-  const int E = (ab >> 7) - 127;
-  int e = E - 8 + ((ab & 0x7F) > 0x60 ? 1 : 0);
-  e = min(max(e, -127), 127);
-
-  union { unsigned u; float f; } inv;
-  inv.u = (unsigned)(127 - e) << 23;  // 2^-e, exact (e <= 121)
+  for (int i = 0; i < 4; ++i) ab = mxq_amax_bits(v[i], ab);
+  const int e = mxq_block_exp(ab);
+  const float inv = mxq_inv_scale(e);
 
   uint4v out[2];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    int w0 = 0, w1 = 0;
-    w0 = __builtin_amdgcn_cvt_pk_fp8_f32(bits2f(v[i][0]) * inv.f,
-                                         bits2f(v[i][1]) * inv.f, w0, false);
-    w0 = __builtin_amdgcn_cvt_pk_fp8_f32(bits2f(v[i][2]) * inv.f,
-                                         bits2f(v[i][3]) * inv.f, w0, true);
-    w1 = __builtin_amdgcn_cvt_pk_fp8_f32(bits2f(v[i][4]) * inv.f,
-                                         bits2f(v[i][5]) * inv.f, w1, false);
-    w1 = __builtin_amdgcn_cvt_pk_fp8_f32(bits2f(v[i][6]) * inv.f,
-                                         bits2f(v[i][7]) * inv.f, w1, true);
-    out[i >> 1][2 * (i & 1)] = (unsigned)w0;
-    out[i >> 1][2 * (i & 1) + 1] = (unsigned)w1;
+    unsigned w0, w1;
+    mxq_cvt8(v[i], inv, w0, w1);
+    out[i >> 1][2 * (i & 1)] = w0;
+    out[i >> 1][2 * (i & 1) + 1] = w1;
   }
   uint4v* dst = (uint4v*)(q + row * K + 32 * kb);
   dst[0] = out[0];
@@ -160,22 +152,6 @@ struct MxStage {
       simg[mx_soff(row, kb)] = (char)(sc >> (8 * kb));
   }
 };
-
-template <typename OutT>
-__device__ __forceinline__ void mx_store4(OutT* p, f32x4 v);
-template <>
-__device__ __forceinline__ void mx_store4<float>(float* p, f32x4 v) {
-  *(f32x4*)p = v;
-}
-template <>
-__device__ __forceinline__ void mx_store4<bf16>(bf16* p, f32x4 v) {
-  uint2 r;
-  r.x = ((unsigned)(unsigned short)f2bits(v[0])) |
-        ((unsigned)(unsigned short)f2bits(v[1]) << 16);
-  r.y = ((unsigned)(unsigned short)f2bits(v[2])) |
-        ((unsigned)(unsigned short)f2bits(v[3]) << 16);
-  *(uint2*)p = r;
-}
 
 // one m-fragment against the four n-fragments; op_sel = fragment index
 #define MX_MMA_ROW(MI)                                                        \

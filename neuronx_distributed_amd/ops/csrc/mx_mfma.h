@@ -48,6 +48,23 @@ __device__ __forceinline__ f32x4 mfma_mx(i32x8 a, i32x8 b, f32x4 c,
       a, b, c, FA, FB, SA, scale_a, SB, scale_b);
 }
 
+// Four consecutive n of one accumulator: 16 (fp32) or 8 (bf16) bytes.
+template <typename OutT>
+__device__ __forceinline__ void mx_store4(OutT* p, f32x4 v);
+template <>
+__device__ __forceinline__ void mx_store4<float>(float* p, f32x4 v) {
+  *(f32x4*)p = v;
+}
+template <>
+__device__ __forceinline__ void mx_store4<bf16>(bf16* p, f32x4 v) {
+  uint2 r;
+  r.x = ((unsigned)(unsigned short)f2bits(v[0])) |
+        ((unsigned)(unsigned short)f2bits(v[1]) << 16);
+  r.y = ((unsigned)(unsigned short)f2bits(v[2])) |
+        ((unsigned)(unsigned short)f2bits(v[3]) << 16);
+  *(uint2*)p = r;
+}
+
 // ---------------------------------------------------------------------------
 // LDS image of a [rows][RB bytes] k-contiguous tile (RB = 128 for an fp8
 // K=128 tile, 64 for the fp4 one).  The 16 lanes that fetch the same

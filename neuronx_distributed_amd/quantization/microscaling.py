@@ -71,7 +71,9 @@ def mx_matmul(a: torch.Tensor, qb: torch.Tensor, b_scales: torch.Tensor,
 
 
 # ---------------------------------------------------------------------------
-# Stored MX format + the MX linear (native kernel: ops/csrc/mx_gemm.hip)
+# Stored MX format + the MX linear (native kernels: ops/csrc/mx_gemm.hip,
+# the 128x128 tile, and ops/csrc/mx_skinny.hip, the M <= 32 decode kernel
+# that quantizes x inside the GEMM; both read the layout below as stored)
 #
 # Public layout contract (what checkpoints and the HIP kernel share):
 #   fp8_e4m3 payload  uint8 (..., K)    one e4m3fn byte per element

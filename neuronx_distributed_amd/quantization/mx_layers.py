@@ -3,9 +3,12 @@
 ``MXColumnParallel`` / ``MXRowParallel`` keep the local weight shard in the
 stored MX format of ``microscaling.pack_mx`` (uint8 payload + uint8 e8m0
 scales, blocks of 32 along K) and run ``microscaling.mx_linear``: on the GPU
-the native block-scaled MFMA GEMM (``ops/csrc/mx_gemm.hip``) with the
-activation quantized to MXFP8 on the fly, elsewhere (CPU, or a local K that
-is not a multiple of 128) the emulation.  The communication pattern is the
+the native block-scaled MFMA GEMM with the activation quantized to MXFP8 on
+the fly -- up to 32 rows (decode) in the fused split-K skinny kernel
+(``ops/csrc/mx_skinny.hip``), more rows through ``mx_quantize_rows`` and the
+128x128 tile (``ops/csrc/mx_gemm.hip``); ``ops.mx_linear`` picks, the layers
+do not change -- elsewhere (CPU, or a local K that is not a multiple of 128)
+the emulation.  The communication pattern is the
 one of ``QuantizedColumnParallel`` / ``QuantizedRowParallel``.
 
 Sharding along K (row parallel) cuts between 32-blocks, so a rank's payload
