@@ -27,6 +27,7 @@ from ..parallel.layers import (
     ColumnParallelLinear,
     RowParallelLinear,
     ParallelEmbedding,
+    wgrad_tn_weight_eligible,
 )
 from ..parallel.qkv_linear import GQAQKVColumnParallelLinear
 from ..parallel.loss_functions import parallel_cross_entropy
@@ -312,13 +313,23 @@ class LlamaMLP(nn.Module):
             config.hidden_size, 2 * config.intermediate_size, bias=False,
             gather_output=False, stride=2, sequence_parallel_enabled=sp,
             init_method=_init_method(config.initializer_range))
+        # wgrad_tn=False: at M = 32768 the K-contiguous wgrad of the
+        # 4096 x 11008 output LOSES (transposes 0.114 + 0.298 + TN 2.871 =
+        # 3.284 ms against NT 3.074 ms, ratio 1.068; profiles/README.md)
         self.down_proj = RowParallelLinear(
             config.intermediate_size, config.hidden_size, bias=False,
             input_is_parallel=True, sequence_parallel_enabled=sp,
+            wgrad_tn=False,
             init_method=_init_method(config.initializer_range))
 
     def forward(self, x):
-        return self.down_proj(ops.swiglu(self.gate_up_proj(x)))
+        # the SwiGLU backward holds dx in registers: it also writes dx^T for
+        # the gate_up weight gradient when that one runs K-contiguous
+        # (a wrapped gate_up_proj, LoRA or quantized, keeps the plain kernel)
+        gu = self.gate_up_proj
+        return self.down_proj(ops.swiglu(
+            gu(x), wgrad_dxt=(type(gu) is ColumnParallelLinear
+                              and wgrad_tn_weight_eligible(gu.weight))))
 
 
 def fused_norm_train_ok(config, hidden, training=True) -> bool:
@@ -489,7 +500,7 @@ class LlamaForCausalLM(nn.Module):
         self.model = LlamaModel(config)
         self.lm_head = ColumnParallelLinear(
             config.hidden_size, config.vocab_size, bias=False,
-            gather_output=False, dgrad_shadow=False,
+            gather_output=False, dgrad_shadow=False, wgrad_tn=False,
             init_method=_init_method(config.initializer_range))
         if config.tie_word_embeddings:
             self.lm_head.weight = self.model.embed_tokens.weight

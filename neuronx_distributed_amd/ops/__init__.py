@@ -359,9 +359,85 @@ def apply_rotary_polar_compatible(query, key, freqs):
 # SwiGLU
 # ---------------------------------------------------------------------------
 
+# One-slot hand-off of dx^T from SwiGLU's backward to the weight-gradient
+# GEMM of the linear that produced its input (parallel/layers.py wgrad_tn).
+# Autograd has no channel for a second gradient, so the slot is keyed by the
+# dx tensor itself: its data pointer, shape, strides and ``_version``.  The
+# slot keeps dx alive, so the pointer cannot be handed out again while the
+# entry exists; every linear backward takes (and thereby empties) the slot
+# first, so an entry lives only between two neighbouring backward nodes.
+_WGRAD_HANDOFF = [None]
+
+
+def wgrad_handoff_put(dx: torch.Tensor, dxt: torch.Tensor) -> None:
+    _WGRAD_HANDOFF[0] = (dx, dx._version, dxt)
+
+
+def wgrad_handoff_take(grad_output: Optional[torch.Tensor] = None):
+    """Empty the slot; return its dx^T iff ``grad_output`` is the very dx it
+    was filled with, unmodified (same memory, shape, strides, version).
+    Anything else (a hook that replaced or edited the gradient, a copy)
+    returns None and the entry is dropped."""
+    entry, _WGRAD_HANDOFF[0] = _WGRAD_HANDOFF[0], None
+    if entry is None or grad_output is None:
+        return None
+    dx, version, dxt = entry
+    if (grad_output.data_ptr() == dx.data_ptr()
+            and grad_output.shape == dx.shape
+            and grad_output.stride() == dx.stride()
+            and grad_output.dtype == dx.dtype
+            and grad_output._version == version
+            and dx._version == version):
+        return dxt
+    return None
+
+
+def swiglu_bwd_t_available() -> bool:
+    lib = _load()
+    return lib is not None and hasattr(lib, "swiglu_bwd_t")
+
+
+def swiglu_bwd_t(x: torch.Tensor, dy: torch.Tensor, dx: torch.Tensor = None,
+                 dxt: torch.Tensor = None):
+    """SwiGLU backward with two outputs: dx (like x) bit-identical to the
+    plain backward kernel, and dxt (2I, N) = dx^T contiguous, written by one
+    tiled kernel (csrc/swiglu.hip).  x (..., 2I), dy (..., I) contiguous
+    bf16 GPU tensors; N (rows) and I multiples of 8."""
+    lib = _require_lib()
+    twoI = x.shape[-1]
+    I = twoI // 2
+    N = x.numel() // max(twoI, 1)
+    if not (x.is_cuda and x.dtype == torch.bfloat16 and x.is_contiguous()
+            and dy.is_cuda and dy.dtype == torch.bfloat16
+            and dy.is_contiguous() and dy.numel() == N * I
+            and twoI == 2 * I and N > 0 and I > 0 and N % 8 == 0
+            and I % 8 == 0):
+        raise ValueError(f"swiglu_bwd_t: x {tuple(x.shape)} / dy "
+                         f"{tuple(dy.shape)} outside the kernel contract "
+                         f"(contiguous bf16 on the GPU, rows and I "
+                         f"multiples of 8)")
+    if dx is None:
+        dx = torch.empty_like(x)
+    if dxt is None:
+        dxt = torch.empty(twoI, N, dtype=x.dtype, device=x.device)
+    for name, t, shape in (("dx", dx, tuple(x.shape)),
+                           ("dxt", dxt, (twoI, N))):
+        if t.dtype != x.dtype or t.device != x.device or \
+                tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"swiglu_bwd_t: {name} must be a contiguous "
+                             f"{shape} bf16 tensor on {x.device}")
+    rc = lib.swiglu_bwd_t(_ptr(x), _ptr(dy), _ptr(dx), _ptr(dxt),
+                          ctypes.c_long(N), ctypes.c_long(I), _stream())
+    if rc != 0:
+        raise ValueError(f"swiglu_bwd_t rejected N={N}, I={I} (16-byte "
+                         f"aligned pointers required)")
+    return dx, dxt
+
+
 class _SwiGLUFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x):
+    def forward(ctx, x, wgrad_dxt=False):
+        ctx.wgrad_dxt = bool(wgrad_dxt)
         ctx.save_for_backward(x)
         I = x.shape[-1] // 2
         if x.is_cuda and x.dtype == torch.bfloat16 and I % 8 == 0:
@@ -380,26 +456,45 @@ class _SwiGLUFn(torch.autograd.Function):
     def backward(ctx, dy):
         (x,) = ctx.saved_tensors
         I = x.shape[-1] // 2
+        # dx^T for the producer's K-contiguous weight gradient: only when the
+        # caller asked for it and that wgrad would take it right now
+        want_t = False
+        if ctx.wgrad_dxt and not torch.is_grad_enabled():
+            from ..parallel.layers import wgrad_tn_wants_dxt
+
+            want_t = wgrad_tn_wants_dxt(x)
         if x.is_cuda and x.dtype == torch.bfloat16 and I % 8 == 0:
             lib = _require_lib()
             dy2 = dy.contiguous()
             N = x.numel() // x.shape[-1]
+            if want_t:
+                dx, dxt = swiglu_bwd_t(x, dy2)
+                wgrad_handoff_put(dx, dxt)
+                return dx, None
             dx = torch.empty_like(x)
             lib.swiglu_bwd(_ptr(x), _ptr(dy2), _ptr(dx), ctypes.c_long(N),
                            ctypes.c_int(I), _stream())
-            return dx
+            return dx, None
         g, u = x[..., :I].float(), x[..., I:].float()
         dyf = dy.float()
         sig = torch.sigmoid(g)
         s = g * sig
         dg = dyf * u * (sig + s * (1 - sig))
         du = dyf * s
-        return torch.cat([dg, du], dim=-1).to(x.dtype)
+        dx = torch.cat([dg, du], dim=-1).to(x.dtype)
+        if want_t:  # composed stand-in for the dual-output kernel
+            wgrad_handoff_put(dx, transpose(dx.reshape(-1, dx.shape[-1])))
+        return dx, None
 
 
-def swiglu(x: torch.Tensor) -> torch.Tensor:
-    """x = [gate; up] on the last dim -> silu(gate)*up."""
-    return _SwiGLUFn.apply(x)
+def swiglu(x: torch.Tensor, wgrad_dxt: bool = False) -> torch.Tensor:
+    """x = [gate; up] on the last dim -> silu(gate)*up.
+
+    ``wgrad_dxt``: x is the output of a linear whose weight gradient may run
+    K-contiguous (``parallel.layers.wgrad_tn``); the backward then also
+    writes dx^T and hands it to that wgrad instead of leaving it to
+    transpose dx again."""
+    return _SwiGLUFn.apply(x, wgrad_dxt)
 
 
 # ---------------------------------------------------------------------------
@@ -619,6 +714,55 @@ def transpose(x: torch.Tensor, out: Optional[torch.Tensor] = None):
     if rc != 0:
         raise ValueError(f"transpose rejected shape {tuple(x.shape)}")
     return out
+
+
+TRANSPOSE_MULTI_MAX = 4  # csrc/transpose.hip TR_MULTI_MAX
+
+
+def transpose_multi(xs, outs=None):
+    """Transpose one to four 2-D matrices (different shapes allowed) in ONE
+    launch whose descriptors are kernel arguments: no device table and no
+    host-to-device copy, unlike :func:`transpose_batched`.  Same contract
+    per matrix as :func:`transpose`; everything is validated before the
+    launch.  Returns the list of (C, R) results."""
+    xs = list(xs)
+    if not 1 <= len(xs) <= TRANSPOSE_MULTI_MAX:
+        raise ValueError(f"transpose_multi: 1 to {TRANSPOSE_MULTI_MAX} "
+                         f"matrices, got {len(xs)}")
+    if outs is None:
+        outs = [torch.empty(x.shape[1], x.shape[0], dtype=x.dtype,
+                            device=x.device) if x.dim() == 2 else None
+                for x in xs]
+    outs = list(outs)
+    if len(outs) != len(xs):
+        raise ValueError("transpose_multi: one destination per source")
+    if not xs[0].is_cuda:
+        for x, o in zip(xs, outs):
+            transpose(x, o)
+        return outs
+    lib = _require_lib()
+    n = len(xs)
+    strides = []
+    for x, o in zip(xs, outs):
+        if o is None or x.device != xs[0].device:
+            raise ValueError("transpose_multi: 2-D sources on one device")
+        _, rs = _transpose_tiles(lib, "transpose_multi", x, o)
+        strides.append(rs)
+    rc = lib.transpose_bf16_multi(
+        (ctypes.c_void_p * n)(*[x.data_ptr() for x in xs]),
+        (ctypes.c_void_p * n)(*[o.data_ptr() for o in outs]),
+        (ctypes.c_long * n)(*strides),
+        (ctypes.c_long * n)(*[x.shape[0] for x in xs]),
+        (ctypes.c_long * n)(*[x.shape[1] for x in xs]),
+        ctypes.c_int(n), _stream())
+    if rc != 0:
+        raise ValueError(f"transpose_multi rejected {n} matrices")
+    return outs
+
+
+def transpose_multi_available() -> bool:
+    lib = _load()
+    return lib is not None and hasattr(lib, "transpose_bf16_multi")
 
 
 def transpose_batched(xs, outs=None):

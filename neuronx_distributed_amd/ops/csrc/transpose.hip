@@ -28,11 +28,7 @@
 // matrix; outside lanes neither load nor store, and no LDS word that was
 // not written is ever stored.
 
-#include "common.h"
-
-typedef unsigned u4v __attribute__((ext_vector_type(4)));
-
-#define TR_TILE 64
+#include "transpose_tile.h"
 
 __device__ __forceinline__ void transpose_tile(
     const short* __restrict__ src, short* __restrict__ dst, long src_stride,
@@ -46,12 +42,7 @@ __device__ __forceinline__ void transpose_tile(
       const short* p = src + (long)r * src_stride + c;
       u4v a = *(const u4v*)p;
       u4v b = *(const u4v*)(p + src_stride);
-      unsigned* w = tile + (8 * ch) * 32 + (rp ^ (ch << 2));
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        w[(2 * k) * 32] = (a[k] & 0xffffu) | (b[k] << 16);
-        w[(2 * k + 1) * 32] = (a[k] >> 16) | (b[k] & 0xffff0000u);
-      }
+      tr_image_put(tile, ch, rp, a, b);
     }
   }
   __syncthreads();
@@ -60,8 +51,7 @@ __device__ __forceinline__ void transpose_tile(
     const int cl = it * 32 + (t >> 3), q = t & 7;
     const int c = c0 + cl, r = r0 + 8 * q;
     if (c < C && r < R) {
-      u4v v = *(const u4v*)(tile + cl * 32 + ((q ^ ((cl >> 3) & 7)) << 2));
-      *(u4v*)(dst + (long)c * R + r) = v;
+      *(u4v*)(dst + (long)c * R + r) = tr_image_get(tile, cl, q);
     }
   }
 }
@@ -69,7 +59,7 @@ __device__ __forceinline__ void transpose_tile(
 extern "C" __global__ void __launch_bounds__(256)
 transpose_bf16_kernel(const short* __restrict__ src, short* __restrict__ dst,
                       long src_stride, int R, int C, int tiles_c) {
-  __shared__ __attribute__((aligned(16))) unsigned tile[TR_TILE * 32];
+  __shared__ __attribute__((aligned(16))) unsigned tile[TR_IMAGE_DWORDS];
   const int b = blockIdx.x;
   transpose_tile(src, dst, src_stride, R, C, b / tiles_c, b % tiles_c, tile);
 }
@@ -80,7 +70,7 @@ transpose_bf16_kernel(const short* __restrict__ src, short* __restrict__ dst,
 
 extern "C" __global__ void __launch_bounds__(256)
 transpose_bf16_batched_kernel(const long* __restrict__ desc, int n) {
-  __shared__ __attribute__((aligned(16))) unsigned tile[TR_TILE * 32];
+  __shared__ __attribute__((aligned(16))) unsigned tile[TR_IMAGE_DWORDS];
   const int b = blockIdx.x;
   // last matrix whose first tile is <= b (block-uniform)
   int lo = 0, hi = n - 1;
@@ -94,6 +84,37 @@ transpose_bf16_batched_kernel(const long* __restrict__ desc, int n) {
   const int local = b - (int)d[5];
   transpose_tile((const short*)d[0], (short*)d[1], d[2], R, C,
                  local / tiles_c, local % tiles_c, tile);
+}
+
+// One launch over up to four matrices whose descriptors travel BY VALUE in
+// the kernel arguments: no device table, so no host-to-device copy per
+// call.  first[i] is the first tile of matrix i (first[0] == 0, ascending;
+// INT_MAX for the unused slots), so a block finds its matrix with at most
+// three compares.
+#define TR_MULTI_MAX 4
+
+struct TrMat {
+  const short* src;
+  short* dst;
+  long src_stride;
+  int R, C;
+};
+
+struct TrMulti {
+  TrMat m[TR_MULTI_MAX];
+  int first[TR_MULTI_MAX];
+};
+
+extern "C" __global__ void __launch_bounds__(256)
+transpose_bf16_multi_kernel(const TrMulti p) {
+  __shared__ __attribute__((aligned(16))) unsigned tile[TR_IMAGE_DWORDS];
+  const int b = blockIdx.x;
+  const int i = (b >= p.first[1]) + (b >= p.first[2]) + (b >= p.first[3]);
+  const TrMat& m = p.m[i];
+  const int tiles_c = (m.C + TR_TILE - 1) / TR_TILE;
+  const int local = b - p.first[i];
+  transpose_tile(m.src, m.dst, m.src_stride, m.R, m.C, local / tiles_c,
+                 local % tiles_c, tile);
 }
 
 static inline long transpose_tiles(long R, long C) {
@@ -116,6 +137,35 @@ extern "C" int transpose_bf16(const void* src, void* dst, long src_stride,
   transpose_bf16_kernel<<<(unsigned)tiles, 256, 0, stream>>>(
       (const short*)src, (short*)dst, src_stride, (int)R, (int)C,
       (int)((C + TR_TILE - 1) / TR_TILE));
+  return 0;
+}
+
+// n in [1, 4] matrices given as host arrays; every matrix is checked against
+// the contract before anything is launched.
+extern "C" int transpose_bf16_multi(const void* const* srcs,
+                                    void* const* dsts,
+                                    const long* src_strides, const long* Rs,
+                                    const long* Cs, int n,
+                                    hipStream_t stream) {
+  if (n < 1 || n > TR_MULTI_MAX) return 1;
+  TrMulti p;
+  long first = 0;
+  for (int i = 0; i < TR_MULTI_MAX; ++i) {
+    if (i >= n) {
+      p.m[i] = TrMat{nullptr, nullptr, 0, 0, 0};
+      p.first[i] = 0x7fffffff;
+      continue;
+    }
+    long tiles = transpose_bf16_tiles(Rs[i], Cs[i], src_strides[i]);
+    if (tiles < 0 || ((uintptr_t)srcs[i] & 15) || ((uintptr_t)dsts[i] & 15))
+      return 1;
+    p.m[i] = TrMat{(const short*)srcs[i], (short*)dsts[i], src_strides[i],
+                   (int)Rs[i], (int)Cs[i]};
+    p.first[i] = (int)first;
+    first += tiles;
+    if (first >= 0x7fffffffL) return 1;
+  }
+  transpose_bf16_multi_kernel<<<(unsigned)first, 256, 0, stream>>>(p);
   return 0;
 }
 

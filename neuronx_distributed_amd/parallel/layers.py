@@ -330,6 +330,96 @@ def _dgrad(grad_output: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
     return F.linear(grad_output, w_t)
 
 
+def _wgrad_tn_enabled() -> bool:
+    return os.environ.get("NXDA_WGRAD_TN", "1") == "1"
+
+
+# Same floor as the dgrad: the 4096x4096 class and up.
+_WGRAD_TN_MIN_NUMEL = 4096 * 4096
+# The contraction runs over the tokens.  The K-contiguous form was measured
+# at M = 32768 only (profiles/README.md); shorter contractions keep dY^T @ X.
+_WGRAD_TN_MIN_M = 16384
+
+
+def wgrad_tn_weight_eligible(weight: torch.Tensor) -> bool:
+    """Weights whose gradient may run K-contiguous: bf16, out*in >=
+    4096x4096, both sizes inside the transpose contract; a weight opts out
+    with ``weight.wgrad_tn = False`` (down_proj, lm_head)."""
+    return (weight.dim() == 2 and weight.dtype == torch.bfloat16
+            and weight.numel() >= _WGRAD_TN_MIN_NUMEL
+            and weight.shape[0] % 8 == 0 and weight.shape[1] % 8 == 0
+            and getattr(weight, "wgrad_tn", True))
+
+
+def _wgrad_tn_operand_ok(t: torch.Tensor) -> bool:
+    """A (tokens, features) operand that ``ops.transpose`` takes: bf16,
+    dense rows with a 16-byte-multiple stride and base, tokens >= the
+    threshold; on the GPU the native transpose must be there, on the CPU the
+    composed fallback stands in for it."""
+    if t.dim() != 2 or t.dtype != torch.bfloat16:
+        return False
+    M, C = t.shape
+    if M < _WGRAD_TN_MIN_M or M % 8 or C % 8 or t.stride(1) != 1 \
+            or t.stride(0) < C or t.stride(0) % 8 or t.data_ptr() % 16:
+        return False
+    if t.is_cuda:
+        from .. import ops as _ops
+
+        return _ops.transpose_multi_available()
+    return True
+
+
+def wgrad_tn_eligible(weight: torch.Tensor, go2d: torch.Tensor,
+                      in2d: torch.Tensor) -> bool:
+    """True when ``grad_weight = go2d^T @ in2d`` runs as ``wgrad_tn``."""
+    if torch.is_grad_enabled():  # double backward differentiates through it
+        return False
+    return (_wgrad_tn_enabled() and wgrad_tn_weight_eligible(weight)
+            and go2d.device == in2d.device
+            and _wgrad_tn_operand_ok(go2d) and _wgrad_tn_operand_ok(in2d))
+
+
+def wgrad_tn_wants_dxt(x: torch.Tensor) -> bool:
+    """Asked by SwiGLU's backward (x = its saved input, the output of the
+    gate_up linear): would that linear's wgrad take a dx^T right now?"""
+    if not _wgrad_tn_enabled() or x.dtype != torch.bfloat16 \
+            or not x.is_contiguous() or x.dim() < 2:
+        return False
+    C = x.shape[-1]
+    M = x.numel() // max(C, 1)
+    if M < _WGRAD_TN_MIN_M or M % 8 or C % 16 or x.data_ptr() % 16:
+        return False
+    if x.is_cuda:
+        from .. import ops as _ops
+
+        return (_ops.swiglu_bwd_t_available()
+                and _ops.transpose_multi_available())
+    return True
+
+
+def wgrad_tn(go2d: torch.Tensor, in2d: torch.Tensor,
+             go_t: Optional[torch.Tensor] = None,
+             in_t: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """grad_weight (out, in) = go2d^T @ in2d as a K-contiguous product.
+
+    ``go2d.t().matmul(in2d)`` walks both operands along their strided
+    dimension (hipBLASLt NT class, a depth-32 tile that re-stages both
+    through LDS).  ``F.linear(go_t, in_t)`` with go_t (out, M) and in_t
+    (in, M) contiguous is the same product in the forward's TN class.
+    Whichever transpose was not handed in is built here, both in one launch
+    (``ops.transpose_multi``), and dropped with the call."""
+    from .. import ops as _ops
+
+    todo = [t for t, have in ((go2d, go_t), (in2d, in_t)) if have is None]
+    if todo:
+        built = _ops.transpose_multi(todo)
+        if go_t is None:
+            go_t = built.pop(0)
+        if in_t is None:
+            in_t = built.pop(0)
+    return F.linear(go_t, in_t)
+
+
 class LinearWithAsyncCommunication(torch.autograd.Function):
     """F.linear with TP/SP collectives placed for overlap.
 
@@ -381,6 +471,11 @@ class LinearWithAsyncCommunication(torch.autograd.Function):
         tp_info = ps.get_group_info("tp")
         handle = None
 
+        # dx^T left by a SwiGLU backward for exactly this grad_output, or
+        # None; taking it empties the slot whatever this backward does next
+        from .. import ops as _ops
+
+        go_t = _ops.wgrad_handoff_take(grad_output)
         grad_output = grad_output.contiguous()
         grad_input = _dgrad(grad_output, weight)
 
@@ -414,7 +509,11 @@ class LinearWithAsyncCommunication(torch.autograd.Function):
         if ctx.compute_weight_gradient:
             go2d = grad_output.reshape(-1, grad_output.shape[-1])
             in2d = total_input.reshape(-1, total_input.shape[-1])
-            grad_weight = go2d.t().matmul(in2d)
+            if wgrad_tn_eligible(weight, go2d, in2d):
+                grad_weight = wgrad_tn(go2d, in2d, go_t=go_t)
+            else:
+                grad_weight = go2d.t().matmul(in2d)
+            go_t = None  # 1.4 GB at gate_up: gone once its GEMM is issued
             if ctx.use_bias:
                 grad_bias = go2d.sum(dim=0)
         elif ctx.use_bias:
@@ -493,7 +592,7 @@ class ColumnParallelLinear(BaseParallelLinear):
     def __init__(self, input_size, output_size, bias=True, gather_output=True,
                  dtype=None, device=None, init_method=None, stride=1,
                  sequence_parallel_enabled=False, keep_master_weight=False,
-                 skip_bias_add=False, dgrad_shadow=True):
+                 skip_bias_add=False, dgrad_shadow=True, wgrad_tn=True):
         super().__init__()
         self.input_size = input_size
         self.output_size = output_size
@@ -501,6 +600,8 @@ class ColumnParallelLinear(BaseParallelLinear):
         # False: the dgrad stays on the strided weight (vocabulary
         # projections: no gain at 32000x4096, profiles/README.md)
         self.dgrad_shadow = dgrad_shadow
+        # False: the wgrad stays dY^T @ X (wgrad_tn_weight_eligible)
+        self.wgrad_tn = wgrad_tn
         self.sequence_parallel_enabled = sequence_parallel_enabled
         self.skip_bias_add = skip_bias_add
         self.stride = stride
@@ -544,6 +645,8 @@ class ColumnParallelLinear(BaseParallelLinear):
             # marked here, not at construction: weight tying replaces the
             # Parameter object after __init__
             self.weight.dgrad_shadow = False
+        if not self.wgrad_tn:
+            self.weight.wgrad_tn = False
         output_parallel = linear_with_async_allreduce(
             input_parallel, self.weight, bias,
             async_grad_allreduce=self.async_tensor_model_parallel_allreduce,
@@ -567,11 +670,13 @@ class RowParallelLinear(BaseParallelLinear):
                  input_is_parallel=True, dtype=None, device=None,
                  init_method=None, stride=1, sequence_parallel_enabled=False,
                  keep_master_weight=False, skip_bias_add=False,
-                 reduce_output=True):
+                 reduce_output=True, wgrad_tn=True):
         super().__init__()
         self.input_size = input_size
         self.output_size = output_size
         self.input_is_parallel = input_is_parallel
+        # False: the wgrad stays dY^T @ X (wgrad_tn_weight_eligible)
+        self.wgrad_tn = wgrad_tn
         self.sequence_parallel_enabled = sequence_parallel_enabled
         self.skip_bias_add = skip_bias_add
         self.reduce_output = reduce_output
@@ -611,6 +716,8 @@ class RowParallelLinear(BaseParallelLinear):
                 and not isinstance(input_parallel, torch.fx.Proxy)):
             return self._forward_sp_overlapped(input_parallel)
 
+        if not self.wgrad_tn:
+            self.weight.wgrad_tn = False
         output_parallel = linear_with_async_allreduce(
             input_parallel, self.weight, None,
             async_grad_allreduce=False, sequence_parallel_enabled=False)

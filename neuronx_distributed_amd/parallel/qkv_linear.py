@@ -24,7 +24,8 @@ import torch.distributed as dist
 from . import comm
 from . import parallel_state as ps
 from .layers import (BaseParallelLinear, default_init_method, _dgrad,
-                     _weight_cache_key, dgrad_weight_t)
+                     _weight_cache_key, dgrad_weight_t, wgrad_tn,
+                     wgrad_tn_eligible)
 from .utils import divide, set_tensor_model_parallel_attributes
 
 
@@ -106,6 +107,10 @@ class _QKVLinearWithAsyncCommunication(torch.autograd.Function):
         tp_info = ps.get_group_info("tp")
         world = tp_info.size
 
+        from .. import ops as _ops
+
+        _ops.wgrad_handoff_take()  # a dx^T left in the slot is not ours
+
         gq = gq.contiguous()
         gk = gk.contiguous()
         gv = gv.contiguous()
@@ -144,9 +149,21 @@ class _QKVLinearWithAsyncCommunication(torch.autograd.Function):
         gq2 = gq.reshape(-1, gq.shape[-1])
         gk2 = gk.reshape(-1, gk.shape[-1])
         gv2 = gv.reshape(-1, gv.shape[-1])
-        gwq = gq2.t().matmul(in2d)
-        gwk = gk2.t().matmul(in2d)
-        gwv = gv2.t().matmul(in2d)
+        # weight gradients: the eligible ones run K-contiguous on X^T, built
+        # ONCE for the three products, in one launch with their dY^T
+        gos, ws = (gq2, gk2, gv2), (wq, wk, wv)
+        tn = [wgrad_tn_eligible(w, g, in2d) for g, w in zip(gos, ws)]
+        gts, in_t = [None, None, None], None
+        if any(tn):
+            built = _ops.transpose_multi(
+                [in2d] + [g for g, on in zip(gos, tn) if on])
+            in_t = built.pop(0)
+            gts = [built.pop(0) if on else None for on in tn]
+        gwq, gwk, gwv = (
+            g.t().matmul(in2d) if g_t is None
+            else wgrad_tn(g, in2d, go_t=g_t, in_t=in_t)
+            for g, g_t in zip(gos, gts))
+        del gts
         gbq = gq2.sum(0) if ctx.use_bias else None
         gbk = gk2.sum(0) if ctx.use_bias else None
         gbv = gv2.sum(0) if ctx.use_bias else None
