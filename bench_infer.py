@@ -12,6 +12,7 @@ N GPUs: python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
 import argparse
 import json
 import os
+import sys
 import time
 
 import torch
@@ -33,7 +34,12 @@ def main():
                         "feedback inside the graph); measured ~4%% slower "
                         "than per-step replay at b32 on MI355X, kept for "
                         "multi-token stepping API coverage")
+    p.add_argument("--kv-format", default="bf16", choices=["bf16", "mxfp8"],
+                   help="KV-cache storage: the model dtype, or MXFP8 (e4m3 "
+                        "+ e8m0 block scales, 0.516 of the bytes) read by "
+                        "the fused MX decode-attention kernel")
     args = p.parse_args()
+    kv_format = None if args.kv_format == "bf16" else args.kv_format
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -112,7 +118,7 @@ def main():
     n_kv_local = cfg.num_key_value_heads * kv_mult // tp
     caches = build_kv_caches(cfg.num_hidden_layers, args.batch, n_kv_local,
                              args.prompt + args.new, cfg.head_dim,
-                             device=device)
+                             device=device, kv_format=kv_format)
     sampler = Sampler(do_sample=False)
 
     t0 = time.perf_counter()
@@ -163,7 +169,12 @@ def main():
             "decode_ms_per_step": round(decode_s / steps * 1000, 3),
             "decode_tokens_per_s": round(args.batch * steps / decode_s, 1),
             "dtype": "bf16" if not args.quantize else "bf16+w8a8-fp8", "data": "synthetic",
+            **({"kv_format": kv_format} if kv_format else {}),
         }), flush=True)
+        if on_gpu:
+            print(f"kv_format={args.kv_format} peak_memory_gb="
+                  f"{torch.cuda.max_memory_allocated() / 1e9:.2f}",
+                  file=sys.stderr, flush=True)
     if on_gpu and os.environ.get("NXDA_TUNE", "0") == "1" and \
             hasattr(torch.cuda.tunable, "write_file"):
         torch.cuda.tunable.write_file()

@@ -32,6 +32,8 @@ def main():
     p.add_argument("--prompt-len", type=int, default=512)
     p.add_argument("--new-tokens", type=int, default=128)
     p.add_argument("--top-k", type=int, default=0, help="0 = greedy")
+    p.add_argument("--kv-format", default="bf16", choices=["bf16", "mxfp8"],
+                   help="KV-cache storage: the model dtype or MXFP8")
     args = p.parse_args()
 
     os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
@@ -67,7 +69,9 @@ def main():
     with torch.no_grad():
         t0 = time.time()
         out = generate(model, prompt, max_new_tokens=args.new_tokens,
-                       sampler=sampler)
+                       sampler=sampler,
+                       kv_format=None if args.kv_format == "bf16"
+                       else args.kv_format)
         if torch.cuda.is_available():
             torch.cuda.synchronize()
         dt = time.time() - t0

@@ -9,6 +9,6 @@ from .functions import (
     shard_checkpoint,
     load_sharded_checkpoint,
 )
-from .kv_cache import (KVCache, RollingKVCache,
+from .kv_cache import (KVCache, MXKVCache, RollingKVCache,
                        build_kv_caches)
 from .generation import generate

@@ -13,13 +13,14 @@ from .kv_cache import build_kv_caches
 @torch.no_grad()
 def generate(model, input_ids: torch.Tensor, max_new_tokens: int = 32,
              sampler: Optional[Sampler] = None, eos_token_id: int = -1,
-             use_cuda_graph: bool = True):
+             use_cuda_graph: bool = True, kv_format=None):
     """model: LlamaForCausalLM-compatible (vocab-parallel logits out).
     input_ids (B, S) on the model's device; returns (B, S+new).
 
     On GPU the per-token decode step is captured in a hipGraph and
     replayed (launch-bound otherwise); pass ``use_cuda_graph=False`` for
-    the eager loop."""
+    the eager loop.  ``kv_format="mxfp8"`` keeps the KV cache in MXFP8
+    (inference.kv_cache.MXKVCache) instead of the model dtype."""
     from ..parallel import parallel_state as ps
     from .decode_graph import GraphDecoder
 
@@ -33,7 +34,8 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int = 32,
     caches = build_kv_caches(cfg.num_hidden_layers, B, n_kv_local,
                              S + max_new_tokens, cfg.head_dim,
                              dtype=model_dtype, device=input_ids.device,
-                             window=getattr(cfg, "sliding_window", None))
+                             window=getattr(cfg, "sliding_window", None),
+                             kv_format=kv_format)
 
     # prefill (eager, flash kernel)
     logits = model(input_ids, kv_caches=caches, pos_offset=0)

@@ -36,11 +36,31 @@ class KVCache:
         return self.k[:, :, :pos + S], self.v[:, :, :pos + S]
 
 
+KV_FORMATS = (None, "mxfp8")
+
+
 def build_kv_caches(n_layers: int, batch: int, n_kv_heads_local: int,
                     max_seq: int, head_dim: int, dtype=torch.bfloat16,
-                    device=None, window=None) -> List[KVCache]:
+                    device=None, window=None, kv_format=None
+                    ) -> List[KVCache]:
     """``window``: sliding-window models get RollingKVCache (O(window)
-    memory per layer) when the window is smaller than max_seq."""
+    memory per layer) when the window is smaller than max_seq.
+
+    ``kv_format``: None stores K/V in ``dtype``; "mxfp8" returns
+    :class:`MXKVCache` (e4m3 payload + e8m0 block scales, 0.516 of the bf16
+    bytes) with ``dtype`` as the compute dtype.  The rolling cache has no
+    MX form."""
+    if kv_format not in KV_FORMATS:
+        raise ValueError(f"kv_format {kv_format!r} not supported (one of "
+                         f"{KV_FORMATS})")
+    if kv_format == "mxfp8":
+        if window is not None and window < max_seq:
+            raise NotImplementedError(
+                "kv_format='mxfp8' with a sliding window smaller than "
+                "max_seq: the rolling cache has no MX form")
+        return [MXKVCache(batch, n_kv_heads_local, max_seq, head_dim, dtype,
+                          device)
+                for _ in range(n_layers)]
     if window is not None and window < max_seq:
         return [RollingKVCache(batch, n_kv_heads_local, int(window),
                                head_dim, dtype, device)
@@ -93,3 +113,93 @@ class RollingKVCache(KVCache):
         # prefill attention runs over the CURRENT chunk directly (the
         # cache held nothing before position 0)
         return k_new, v_new
+
+
+class MXKVCache(KVCache):
+    """One layer's cache in MXFP8: 0.516 of the bf16 bytes at D = 128.
+
+    ``k``, ``v``: uint8 (B, Hkv, S_max, D), the e4m3 payload; ``k_scale``,
+    ``v_scale``: uint8 (B, Hkv, S_max, D/32), biased e8m0.  Blocks of 32 run
+    along D; the layout is exactly
+    ``pack_mx(*quantize_mx(x, "fp8_e4m3"), "fp8_e4m3")`` of the (..., D)
+    rows, which is also what the fused decode kernel
+    (ops.decode_attn_mx_step) reads and appends.  ``dtype`` is the compute
+    dtype of the dequantized views.
+
+    The cache is the single source of truth: ``update`` returns DEQUANTIZED
+    views of what it holds, the rows just written included, so prefill,
+    eager decode, chunked verification and the fused kernel all attend to
+    the same values.  On every path but the fused kernel that view is a
+    transient copy in ``dtype`` of the rows it covers ([0, pos + S) for an
+    int ``pos``, the whole buffer for a tensor ``pos``); only the fused
+    kernel streams the quantized bytes.
+
+    bf16 GPU tensors are quantized by the native kernels (ops.mx_kv_store
+    for an int ``pos``, ops.mx_quantize_rows for a tensor ``pos``); CPU
+    tensors and other dtypes go through quantization.microscaling."""
+
+    def __init__(self, batch: int, n_kv_heads: int, max_seq: int,
+                 head_dim: int, dtype=torch.bfloat16, device=None):
+        if head_dim < 32 or head_dim % 32 != 0:
+            raise ValueError(f"MXKVCache: head_dim {head_dim} must be a "
+                             f"multiple of the MX block (32)")
+        device = device or (torch.device("cuda") if torch.cuda.is_available()
+                            else "cpu")
+        self.k = torch.zeros(batch, n_kv_heads, max_seq, head_dim,
+                             dtype=torch.uint8, device=device)
+        self.v = torch.zeros_like(self.k)
+        self.k_scale = torch.zeros(batch, n_kv_heads, max_seq, head_dim // 32,
+                                   dtype=torch.uint8, device=device)
+        self.v_scale = torch.zeros_like(self.k_scale)
+        self.max_seq = max_seq
+        self.dtype = dtype
+
+    @staticmethod
+    def _native(x: torch.Tensor) -> bool:
+        return x.is_cuda and x.dtype == torch.bfloat16
+
+    @staticmethod
+    def _quantize(x: torch.Tensor):
+        """(..., D) -> (payload, scales) uint8 in the stored layout."""
+        if MXKVCache._native(x):
+            from .. import ops
+
+            return ops.mx_quantize_rows(x.contiguous())
+        from ..quantization.microscaling import pack_mx, quantize_mx
+
+        return pack_mx(*quantize_mx(x, "fp8_e4m3"), "fp8_e4m3")
+
+    def _dequantize(self, payload: torch.Tensor, scale: torch.Tensor):
+        from ..quantization.microscaling import dequantize_mx, unpack_mx
+
+        return dequantize_mx(*unpack_mx(payload, scale, "fp8_e4m3"),
+                             dtype=self.dtype)
+
+    def update(self, k_new: torch.Tensor, v_new: torch.Tensor, pos):
+        """Same signature and modes as :meth:`KVCache.update`; the returned
+        K, V are dequantized copies in ``dtype`` (class docstring)."""
+        if isinstance(pos, torch.Tensor):
+            kq, ks = self._quantize(k_new)
+            vq, vs = self._quantize(v_new)
+            self.k.index_copy_(2, pos, kq)
+            self.k_scale.index_copy_(2, pos, ks)
+            self.v.index_copy_(2, pos, vq)
+            self.v_scale.index_copy_(2, pos, vs)
+            return (self._dequantize(self.k, self.k_scale),
+                    self._dequantize(self.v, self.v_scale))
+        S = k_new.shape[2]
+        if self._native(k_new) and self._native(v_new):
+            from .. import ops
+
+            ops.mx_kv_store(k_new, v_new, self.k, self.k_scale, self.v,
+                            self.v_scale, pos)
+        else:
+            kq, ks = self._quantize(k_new)
+            vq, vs = self._quantize(v_new)
+            self.k[:, :, pos:pos + S] = kq
+            self.k_scale[:, :, pos:pos + S] = ks
+            self.v[:, :, pos:pos + S] = vq
+            self.v_scale[:, :, pos:pos + S] = vs
+        end = pos + S
+        return (self._dequantize(self.k[:, :, :end], self.k_scale[:, :, :end]),
+                self._dequantize(self.v[:, :, :end], self.v_scale[:, :, :end]))

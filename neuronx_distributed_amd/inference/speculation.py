@@ -24,10 +24,12 @@ def _greedy(logits: torch.Tensor) -> torch.Tensor:
 
 @torch.no_grad()
 def speculative_generate(target, draft, input_ids: torch.Tensor,
-                         max_new_tokens: int = 32, spec_len: int = 4):
+                         max_new_tokens: int = 32, spec_len: int = 4,
+                         kv_format=None):
     """Greedy speculative generation.  target/draft:
     LlamaForCausalLM-compatible; input_ids (B, S).  Returns
-    (tokens (B, S+new), acceptance_rate)."""
+    (tokens (B, S+new), acceptance_rate).  ``kv_format``: the cache format
+    of both models (build_kv_caches)."""
     B, S = input_ids.shape
 
     def make_caches(model):
@@ -39,7 +41,8 @@ def speculative_generate(target, draft, input_ids: torch.Tensor,
         n_kv_local = cfg.num_key_value_heads * kv_mult // tp
         return build_kv_caches(cfg.num_hidden_layers, B, n_kv_local,
                                S + max_new_tokens + spec_len + 1,
-                               cfg.head_dim, device=input_ids.device)
+                               cfg.head_dim, device=input_ids.device,
+                               kv_format=kv_format)
 
     t_caches = make_caches(target)
     d_caches = make_caches(draft)
@@ -102,7 +105,7 @@ def speculative_generate(target, draft, input_ids: torch.Tensor,
 
 @torch.no_grad()
 def medusa_generate(target, medusa_heads, input_ids: torch.Tensor,
-                    max_new_tokens: int = 32):
+                    max_new_tokens: int = 32, kv_format=None):
     """Medusa-style speculation: ``medusa_heads`` (iterable of
     utils.medusa_utils.MedusaHead, head i predicting the token at offset
     i+2) propose a chain from the LAST HIDDEN STATE in one shot — no
@@ -124,7 +127,7 @@ def medusa_generate(target, medusa_heads, input_ids: torch.Tensor,
     n_kv_local = cfg.num_key_value_heads * kv_mult // tp
     caches = build_kv_caches(cfg.num_hidden_layers, B, n_kv_local,
                              S + max_new_tokens + k + 1, cfg.head_dim,
-                             device=input_ids.device)
+                             device=input_ids.device, kv_format=kv_format)
 
     hidden = target.model(input_ids, pos_offset=0, kv_caches=caches)
     tok = sampler(target.lm_head(hidden)[:, -1, :])

@@ -239,14 +239,25 @@ class LlamaAttention(nn.Module):
         hipGraph and replayed with only memory updates between steps.
 
         On GPU with D=128 the whole chain (RoPE + cache append +
-        flash-decode + GQA) is ONE fused HIP kernel (ops.decode_attn_step);
-        the torch chain below is the CPU/odd-shape reference."""
+        flash-decode + GQA) is ONE fused HIP kernel, chosen by the cache's
+        type: ops.decode_attn_step for a plain bf16 KVCache,
+        ops.decode_attn_mx_step for an MXKVCache.  Any other cache, and the
+        CPU and odd shapes, take the torch chain below (the reference)."""
+        from ..inference.kv_cache import KVCache, MXKVCache
+
         B = q.shape[0]
         rep = self.num_heads_local // self.num_kv_local
-        if (q.is_cuda and self.head_dim == 128 and rep in (1, 2, 4, 8)
-                and q.dtype == torch.bfloat16 and kv_cache is not None
-                and self.sliding_window is None
-                and ops.decode_attn_available()):
+        fusable = (q.is_cuda and self.head_dim == 128 and rep in (1, 2, 4, 8)
+                   and q.dtype == torch.bfloat16
+                   and self.sliding_window is None)
+        fused_bf16 = (fusable and type(kv_cache) is KVCache
+                      and kv_cache.k.is_cuda
+                      and kv_cache.k.dtype == torch.bfloat16
+                      and ops.decode_attn_available())
+        fused_mx = (fusable and type(kv_cache) is MXKVCache
+                    and kv_cache.k.is_cuda
+                    and ops.decode_attn_mx_available())
+        if fused_bf16 or fused_mx:
             def _flat(t):
                 # (B,1,h,D) -> (B, h*D) as a VIEW even for fused-QKV slices
                 # (batch stride may exceed h*D; decode_attn takes strides)
@@ -254,10 +265,16 @@ class LlamaAttention(nn.Module):
                 f = t.reshape(B, -1)
                 return f if f.stride(1) == 1 else t.contiguous().view(B, -1)
 
-            out = ops.decode_attn_step(
-                _flat(q), _flat(k), _flat(v), kv_cache.k, kv_cache.v,
-                cos, sin, pos_t.reshape(1), self.num_heads_local,
-                self.num_kv_local, 1.0 / math.sqrt(self.head_dim))
+            tail = (cos, sin, pos_t.reshape(1), self.num_heads_local,
+                    self.num_kv_local, 1.0 / math.sqrt(self.head_dim))
+            if fused_mx:
+                out = ops.decode_attn_mx_step(
+                    _flat(q), _flat(k), _flat(v), kv_cache.k,
+                    kv_cache.k_scale, kv_cache.v, kv_cache.v_scale, *tail)
+            else:
+                out = ops.decode_attn_step(
+                    _flat(q), _flat(k), _flat(v), kv_cache.k, kv_cache.v,
+                    *tail)
             out = out.unsqueeze(1)  # (B, 1, H*D)
             if sp:
                 out = out.transpose(0, 1)

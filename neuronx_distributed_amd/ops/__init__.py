@@ -934,6 +934,13 @@ def decode_attn_step(q2: torch.Tensor, k2: torch.Tensor, v2: torch.Tensor,
     output): only the last dim must be dense (stride 1)."""
     lib = _require_lib()
     B = q2.shape[0]
+    for name, t in (("kcache", kcache), ("vcache", vcache)):
+        # an MXKVCache's uint8 buffers are half as large: the kernel would
+        # run past them
+        if t.dtype != torch.bfloat16 or t.dim() != 4 or t.shape[-1] != 128:
+            raise ValueError(f"decode_attn_step: {name} must be a bf16 "
+                             f"(B, Hkv, Smax, 128) cache, got {t.dtype} "
+                             f"{tuple(t.shape)}")
     Smax = kcache.shape[2]
     assert Hq // Hkv in (1, 2, 4, 8), "GQA rep must be 1/2/4/8"
     assert cos.dtype == torch.float32 and pos_t.dtype == torch.int64
@@ -1235,3 +1242,156 @@ def mx_linear(x: torch.Tensor, w_payload: torch.Tensor,
                           w_payload, w_scales, fmt, bias32, out_dtype, M, N,
                           K)
     return out.reshape(*x.shape[:-1], N)
+
+
+# ---------------------------------------------------------------------------
+# MXFP8 KV cache: fused decode attention + prefill store
+# (csrc/decode_attn_mx.hip)
+# ---------------------------------------------------------------------------
+
+_MXKV_D = 128  # head dim of the fused decode kernel
+
+
+def decode_attn_mx_available() -> bool:
+    lib = _load()
+    return (lib is not None and hasattr(lib, "decode_attn_mx")
+            and hasattr(lib, "mx_kv_store"))
+
+
+def _mxkv_check_cache(who, k_payload, k_scale, v_payload, v_scale):
+    """The four buffers of an MXKVCache: dense uint8 (B, Hkv, Smax, D) and
+    (B, Hkv, Smax, D/32) on one GPU.  Returns (B, Hkv, Smax, D)."""
+    for name, t in (("k_payload", k_payload), ("k_scale", k_scale),
+                    ("v_payload", v_payload), ("v_scale", v_scale)):
+        _mx_check_dense(f"{who}: {name}", t, torch.uint8)
+        if t.dim() != 4 or t.device != k_payload.device:
+            raise ValueError(f"{who}: {name} must be 4-D on "
+                             f"{k_payload.device}, got {tuple(t.shape)} on "
+                             f"{t.device}")
+    B, Hkv, Smax, D = k_payload.shape
+    if D < 32 or D % 32 or min(B, Hkv, Smax) < 1:
+        raise ValueError(f"{who}: payload {tuple(k_payload.shape)} needs "
+                         f"D % 32 == 0 and non-empty dims")
+    if tuple(v_payload.shape) != (B, Hkv, Smax, D) or \
+            tuple(k_scale.shape) != (B, Hkv, Smax, D // 32) or \
+            tuple(v_scale.shape) != (B, Hkv, Smax, D // 32):
+        raise ValueError(
+            f"{who}: v_payload {tuple(v_payload.shape)}, k_scale "
+            f"{tuple(k_scale.shape)}, v_scale {tuple(v_scale.shape)} do not "
+            f"match k_payload {tuple(k_payload.shape)}")
+    return B, Hkv, Smax, D
+
+
+def decode_attn_mx_step(q2: torch.Tensor, k2: torch.Tensor, v2: torch.Tensor,
+                        k_payload: torch.Tensor, k_scale: torch.Tensor,
+                        v_payload: torch.Tensor, v_scale: torch.Tensor,
+                        cos: torch.Tensor, sin: torch.Tensor,
+                        pos_t: torch.Tensor, Hq: int, Hkv: int,
+                        scale: float) -> torch.Tensor:
+    """:func:`decode_attn_step` over an MXFP8 cache (``MXKVCache`` buffers:
+    e4m3 payload (B, Hkv, Smax, 128) + e8m0 scales (B, Hkv, Smax, 4), both
+    uint8).  The new K (after RoPE) and V rows are quantized and appended at
+    ``pos_t``; their bytes equal ``pack_mx(quantize_mx(row))``, and the
+    output attends to the cache as stored, the new row included.  Everything
+    is validated here; a wrong dtype or shape raises ValueError and launches
+    nothing."""
+    lib = _require_lib()
+    who = "decode_attn_mx_step"
+    if not decode_attn_mx_available():
+        raise RuntimeError("nxd_ops library has no decode_attn_mx — rebuild")
+    B, Hkv_c, Smax, D = _mxkv_check_cache(who, k_payload, k_scale, v_payload,
+                                          v_scale)
+    dev = k_payload.device
+    if D != _MXKV_D or Hkv_c != Hkv or Hkv < 1 or Hq % Hkv \
+            or Hq // Hkv not in (1, 2, 4, 8):
+        raise ValueError(f"{who}: cache {tuple(k_payload.shape)} with "
+                         f"Hq={Hq}, Hkv={Hkv} outside the kernel contract "
+                         f"(D = 128, GQA rep 1/2/4/8)")
+    for name, t, width in (("q2", q2, Hq * D), ("k2", k2, Hkv * D),
+                           ("v2", v2, Hkv * D)):
+        if t.dtype != torch.bfloat16 or t.device != dev or t.dim() != 2 \
+                or tuple(t.shape) != (B, width) or t.stride(1) != 1 \
+                or (B > 1 and t.stride(0) < width) or t.data_ptr() % 2:
+            raise ValueError(f"{who}: {name} must be a bf16 ({B}, {width}) "
+                             f"tensor on {dev} with a dense last dim, got "
+                             f"{t.dtype} {tuple(t.shape)} strides "
+                             f"{t.stride()} on {t.device}")
+    if B > 1 and k2.stride(0) != v2.stride(0):
+        raise ValueError(f"{who}: k2 and v2 must share a row stride, got "
+                         f"{k2.stride(0)} and {v2.stride(0)}")
+    for name, t in (("cos", cos), ("sin", sin)):
+        _mx_check_dense(f"{who}: {name}", t, torch.float32)
+        if t.device != dev or t.dim() != 2 or t.shape[1] != D // 2 \
+                or t.shape[0] < Smax:
+            raise ValueError(f"{who}: {name} {tuple(t.shape)} on {t.device} "
+                             f"must be (>= {Smax}, {D // 2}) on {dev}: the "
+                             f"RoPE table covers the cache")
+    if pos_t.dtype != torch.int64 or pos_t.device != dev \
+            or pos_t.numel() != 1:
+        raise ValueError(f"{who}: pos_t must be one int64 on {dev}, got "
+                         f"{pos_t.dtype} {tuple(pos_t.shape)} on "
+                         f"{pos_t.device}")
+    rep = Hq // Hkv
+    # split-KV workspace (4 splits, shared with decode_attn.hip's merge):
+    # cached-alloc tensors with static shapes, hipGraph-capturable
+    part_o = torch.empty(B * Hkv * 4, rep, D, dtype=torch.float32, device=dev)
+    part_ml = torch.empty(B * Hkv * 4, rep, 2, dtype=torch.float32,
+                          device=dev)
+    out = torch.empty(B, Hq * D, dtype=torch.bfloat16, device=dev)
+    qs = int(q2.stride(0)) if B > 1 else Hq * D
+    kvs = int(k2.stride(0)) if B > 1 else Hkv * D
+    rc = lib.decode_attn_mx(_ptr(q2), _ptr(k2), _ptr(v2), _ptr(k_payload),
+                            _ptr(k_scale), _ptr(v_payload), _ptr(v_scale),
+                            _ptr(cos), _ptr(sin), _ptr(pos_t), _ptr(part_o),
+                            _ptr(part_ml), _ptr(out), B, Hq, Hkv, Smax,
+                            ctypes.c_float(scale), qs, kvs, _stream())
+    if rc != 0:
+        raise ValueError(f"decode_attn_mx rejected B={B}, Hq={Hq}, "
+                         f"Hkv={Hkv}, Smax={Smax}")
+    return out
+
+
+def mx_kv_store(k: torch.Tensor, v: torch.Tensor, k_payload: torch.Tensor,
+                k_scale: torch.Tensor, v_payload: torch.Tensor,
+                v_scale: torch.Tensor, pos: int) -> None:
+    """Quantize bf16 k, v (B, Hkv, S, D) to MXFP8 straight into cache rows
+    [pos, pos + S) in one launch.  k and v may be any strided views with a
+    dense last dim (the models hand in transposes of (B, S, Hkv, D));
+    strides must be multiples of 8 elements.  Written bytes equal
+    ``pack_mx(*quantize_mx(x, "fp8_e4m3"))``.  Contract violations raise
+    ValueError and launch nothing."""
+    lib = _require_lib()
+    who = "mx_kv_store"
+    if not decode_attn_mx_available():
+        raise RuntimeError("nxd_ops library has no mx_kv_store — rebuild")
+    B, Hkv, Smax, D = _mxkv_check_cache(who, k_payload, k_scale, v_payload,
+                                        v_scale)
+    dev = k_payload.device
+    if k.dim() != 4 or tuple(k.shape[:2]) != (B, Hkv) or k.shape[3] != D \
+            or k.shape[2] < 1 or tuple(v.shape) != tuple(k.shape):
+        raise ValueError(f"{who}: k {tuple(k.shape)} / v {tuple(v.shape)} do "
+                         f"not match the cache {tuple(k_payload.shape)}")
+    S = k.shape[2]
+    pos = int(pos)
+    if pos < 0 or pos + S > Smax:
+        raise ValueError(f"{who}: rows [{pos}, {pos + S}) outside the cache "
+                         f"of {Smax} rows")
+    for name, t in (("k", k), ("v", v)):
+        if t.dtype != torch.bfloat16 or t.device != dev:
+            raise ValueError(f"{who}: {name} must be bf16 on {dev}, got "
+                             f"{t.dtype} on {t.device}")
+        if t.stride(3) != 1 or any(st < 0 or st % 8 for st in t.stride()[:3]) \
+                or t.data_ptr() % 16:
+            raise ValueError(f"{who}: {name} needs a dense last dim, strides "
+                             f"that are multiples of 8 and 16-byte "
+                             f"alignment, got strides {t.stride()}")
+    rc = lib.mx_kv_store(_ptr(k), _ptr(v),
+                         (ctypes.c_long * 4)(*k.stride()),
+                         (ctypes.c_long * 4)(*v.stride()),
+                         _ptr(k_payload), _ptr(k_scale), _ptr(v_payload),
+                         _ptr(v_scale), B, Hkv, S, D, Smax,
+                         ctypes.c_long(pos), _stream())
+    if rc != 0:
+        raise ValueError(f"mx_kv_store rejected k {tuple(k.shape)} strides "
+                         f"{k.stride()} at pos {pos}, cache "
+                         f"{tuple(k_payload.shape)}")

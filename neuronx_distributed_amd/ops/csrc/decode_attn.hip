@@ -301,3 +301,28 @@ extern "C" void decode_attn(const void* qlin, const void* klin,
   }
 #undef LAUNCH
 }
+
+// Phase 2 on its own, for phase-1 kernels of other cache formats
+// (decode_attn_mx.hip): the fp32 partials carry no trace of the format.
+// Returns non-zero, launching nothing, if the caller's split count is not
+// the one decode_attn_merge was built for or rep is not 1/2/4/8.
+extern "C" int decode_attn_merge_launch(const void* part_o,
+                                        const void* part_ml, void* outp,
+                                        int B, int Hq, int Hkv, int splits,
+                                        hipStream_t stream) {
+  if (splits != DA_SPLIT || B < 1 || Hkv < 1 || Hq % Hkv != 0) return 1;
+  dim3 grid2(B * Hkv);
+#define LAUNCH(R)                                                        \
+  decode_attn_merge<R><<<grid2, 256, 0, stream>>>(                       \
+      (const float*)part_o, (const float*)part_ml, (short*)outp, B, Hq,  \
+      Hkv)
+  switch (Hq / Hkv) {
+    case 1: LAUNCH(1); break;
+    case 2: LAUNCH(2); break;
+    case 4: LAUNCH(4); break;
+    case 8: LAUNCH(8); break;
+    default: return 1;
+  }
+#undef LAUNCH
+  return 0;
+}

@@ -83,7 +83,8 @@ def mx_matmul(a: torch.Tensor, qb: torch.Tensor, b_scales: torch.Tensor,
 #   scales            uint8 (..., K/32) biased e8m0: byte = scale + 127
 #                                       (0..254; 255 never occurs)
 # Supported natively: fp8_e4m3 activations x {fp8_e4m3, fp4_e2m1} weights,
-# forward only.  fp6 / e5m2, backward and grouped (MoE) MX GEMMs are out of
+# forward only; and the fp8_e4m3 layout as KV-cache storage along head_dim
+# (inference/kv_cache.py MXKVCache, ops/csrc/decode_attn_mx.hip).  fp6 / e5m2, backward and grouped (MoE) MX GEMMs are out of
 # scope; mx_matmul and moe.blockwise_mm_mx keep their emulation.
 # ---------------------------------------------------------------------------
 
