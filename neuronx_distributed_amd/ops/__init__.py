@@ -920,6 +920,59 @@ def decode_attn_available() -> bool:
     return lib is not None and hasattr(lib, "decode_attn")
 
 
+_DA_D = 128     # head dim of the fused decode kernels
+_DA_SPLIT = 4   # DA_SPLIT of csrc/decode_attn_common.h
+
+
+def _decode_attn_check(who, q2, k2, v2, cos, sin, pos_t, B, Hq, Hkv, Smax,
+                       dev):
+    """Everything but the cache, for both fused decode kernels.  Returns the
+    (q, kv) row strides to launch with: the dense widths when B = 1."""
+    D = _DA_D
+    if Hkv < 1 or Hq % Hkv or Hq // Hkv not in (1, 2, 4, 8):
+        raise ValueError(f"{who}: Hq={Hq}, Hkv={Hkv} outside the kernel "
+                         f"contract (GQA rep 1/2/4/8)")
+    for name, t, width in (("q2", q2, Hq * D), ("k2", k2, Hkv * D),
+                           ("v2", v2, Hkv * D)):
+        if t.dtype != torch.bfloat16 or t.device != dev or t.dim() != 2 \
+                or tuple(t.shape) != (B, width) or t.stride(1) != 1 \
+                or (B > 1 and t.stride(0) < width) or t.data_ptr() % 2:
+            raise ValueError(f"{who}: {name} must be a bf16 ({B}, {width}) "
+                             f"tensor on {dev} with a dense last dim, got "
+                             f"{t.dtype} {tuple(t.shape)} strides "
+                             f"{t.stride()} on {t.device}")
+    if B > 1 and k2.stride(0) != v2.stride(0):
+        raise ValueError(f"{who}: k2 and v2 must share a row stride, got "
+                         f"{k2.stride(0)} and {v2.stride(0)}")
+    for name, t in (("cos", cos), ("sin", sin)):
+        _mx_check_dense(f"{who}: {name}", t, torch.float32)
+        if t.device != dev or t.dim() != 2 or t.shape[1] != D // 2 \
+                or t.shape[0] < Smax:
+            raise ValueError(f"{who}: {name} {tuple(t.shape)} on {t.device} "
+                             f"must be (>= {Smax}, {D // 2}) on {dev}: the "
+                             f"RoPE table covers the cache")
+    if pos_t.dtype != torch.int64 or pos_t.device != dev \
+            or pos_t.numel() != 1:
+        raise ValueError(f"{who}: pos_t must be one int64 on {dev}, got "
+                         f"{pos_t.dtype} {tuple(pos_t.shape)} on "
+                         f"{pos_t.device}")
+    if B > 1:
+        return int(q2.stride(0)), int(k2.stride(0))
+    return Hq * D, Hkv * D
+
+
+def _decode_attn_workspace(B, Hq, Hkv, dev):
+    """(part_o, part_ml, out); static shapes from the caching allocator, so
+    the pair of launches is hipGraph-capturable."""
+    rep = Hq // Hkv
+    part_o = torch.empty(B * Hkv * _DA_SPLIT, rep, _DA_D,
+                         dtype=torch.float32, device=dev)
+    part_ml = torch.empty(B * Hkv * _DA_SPLIT, rep, 2, dtype=torch.float32,
+                          device=dev)
+    out = torch.empty(B, Hq * _DA_D, dtype=torch.bfloat16, device=dev)
+    return part_o, part_ml, out
+
+
 def decode_attn_step(q2: torch.Tensor, k2: torch.Tensor, v2: torch.Tensor,
                      kcache: torch.Tensor, vcache: torch.Tensor,
                      cos: torch.Tensor, sin: torch.Tensor,
@@ -928,40 +981,39 @@ def decode_attn_step(q2: torch.Tensor, k2: torch.Tensor, v2: torch.Tensor,
     """One fused decode-attention step: RoPE(q,k) + cache append at the
     device position ``pos_t`` + flash-decode over the cache + GQA.
     q2 (B, Hq*128), k2/v2 (B, Hkv*128) bf16 pre-rope; kcache/vcache
-    (B, Hkv, Smax, 128); cos/sin (Smax, 64) fp32 -> out (B, Hq*128).
+    (B, Hkv, Smax, 128); cos/sin (>= Smax, 64) fp32 -> out (B, Hq*128).
 
     q2/k2/v2 may be row-strided views (e.g. slices of one fused-QKV GEMM
-    output): only the last dim must be dense (stride 1)."""
+    output): only the last dim must be dense (stride 1).  A wrong dtype or
+    shape raises ValueError and launches nothing."""
     lib = _require_lib()
-    B = q2.shape[0]
+    who = "decode_attn_step"
     for name, t in (("kcache", kcache), ("vcache", vcache)):
         # an MXKVCache's uint8 buffers are half as large: the kernel would
         # run past them
-        if t.dtype != torch.bfloat16 or t.dim() != 4 or t.shape[-1] != 128:
-            raise ValueError(f"decode_attn_step: {name} must be a bf16 "
-                             f"(B, Hkv, Smax, 128) cache, got {t.dtype} "
-                             f"{tuple(t.shape)}")
-    Smax = kcache.shape[2]
-    assert Hq // Hkv in (1, 2, 4, 8), "GQA rep must be 1/2/4/8"
-    assert cos.dtype == torch.float32 and pos_t.dtype == torch.int64
-    assert cos.shape[0] >= Smax, (
-        f"RoPE table ({cos.shape[0]}) shorter than KV cache ({Smax})")
-    assert q2.stride(1) == 1 and k2.stride(1) == 1 and v2.stride(1) == 1
-    assert k2.stride(0) == v2.stride(0)
-    rep = Hq // Hkv
-    # split-KV workspace (4 splits; see decode_attn.hip) — cached-alloc
-    # tensors with static shapes, so the pair of launches is
-    # hipGraph-capturable
-    part_o = torch.empty(B * Hkv * 4, rep, 128, dtype=torch.float32,
-                         device=q2.device)
-    part_ml = torch.empty(B * Hkv * 4, rep, 2, dtype=torch.float32,
-                          device=q2.device)
-    out = torch.empty(B, Hq * 128, dtype=torch.bfloat16, device=q2.device)
-    lib.decode_attn(_ptr(q2), _ptr(k2), _ptr(v2), _ptr(kcache), _ptr(vcache),
-                    _ptr(cos), _ptr(sin), _ptr(pos_t), _ptr(part_o),
-                    _ptr(part_ml), _ptr(out), B, Hq, Hkv,
-                    Smax, ctypes.c_float(scale), int(q2.stride(0)),
-                    int(k2.stride(0)), _stream())
+        if t.dtype != torch.bfloat16 or t.dim() != 4 \
+                or t.shape[-1] != _DA_D or not t.is_cuda \
+                or not t.is_contiguous():
+            raise ValueError(f"{who}: {name} must be a contiguous bf16 "
+                             f"(B, Hkv, Smax, 128) GPU cache, got {t.dtype} "
+                             f"{tuple(t.shape)} on {t.device}")
+    if vcache.shape != kcache.shape or vcache.device != kcache.device \
+            or kcache.shape[1] != Hkv or min(kcache.shape) < 1:
+        raise ValueError(f"{who}: kcache {tuple(kcache.shape)} and vcache "
+                         f"{tuple(vcache.shape)} must be one non-empty shape "
+                         f"on one GPU with Hkv={Hkv} heads")
+    B, _, Smax, _ = kcache.shape
+    dev = kcache.device
+    qs, kvs = _decode_attn_check(who, q2, k2, v2, cos, sin, pos_t, B, Hq, Hkv,
+                                 Smax, dev)
+    part_o, part_ml, out = _decode_attn_workspace(B, Hq, Hkv, dev)
+    rc = lib.decode_attn(_ptr(q2), _ptr(k2), _ptr(v2), _ptr(kcache),
+                         _ptr(vcache), _ptr(cos), _ptr(sin), _ptr(pos_t),
+                         _ptr(part_o), _ptr(part_ml), _ptr(out), B, Hq, Hkv,
+                         Smax, ctypes.c_float(scale), qs, kvs, _stream())
+    if rc != 0:
+        raise ValueError(f"decode_attn rejected B={B}, Hq={Hq}, Hkv={Hkv}, "
+                         f"Smax={Smax}")
     return out
 
 
@@ -1249,9 +1301,6 @@ def mx_linear(x: torch.Tensor, w_payload: torch.Tensor,
 # (csrc/decode_attn_mx.hip)
 # ---------------------------------------------------------------------------
 
-_MXKV_D = 128  # head dim of the fused decode kernel
-
-
 def decode_attn_mx_available() -> bool:
     lib = _load()
     return (lib is not None and hasattr(lib, "decode_attn_mx")
@@ -1302,44 +1351,12 @@ def decode_attn_mx_step(q2: torch.Tensor, k2: torch.Tensor, v2: torch.Tensor,
     B, Hkv_c, Smax, D = _mxkv_check_cache(who, k_payload, k_scale, v_payload,
                                           v_scale)
     dev = k_payload.device
-    if D != _MXKV_D or Hkv_c != Hkv or Hkv < 1 or Hq % Hkv \
-            or Hq // Hkv not in (1, 2, 4, 8):
+    if D != _DA_D or Hkv_c != Hkv:
         raise ValueError(f"{who}: cache {tuple(k_payload.shape)} with "
-                         f"Hq={Hq}, Hkv={Hkv} outside the kernel contract "
-                         f"(D = 128, GQA rep 1/2/4/8)")
-    for name, t, width in (("q2", q2, Hq * D), ("k2", k2, Hkv * D),
-                           ("v2", v2, Hkv * D)):
-        if t.dtype != torch.bfloat16 or t.device != dev or t.dim() != 2 \
-                or tuple(t.shape) != (B, width) or t.stride(1) != 1 \
-                or (B > 1 and t.stride(0) < width) or t.data_ptr() % 2:
-            raise ValueError(f"{who}: {name} must be a bf16 ({B}, {width}) "
-                             f"tensor on {dev} with a dense last dim, got "
-                             f"{t.dtype} {tuple(t.shape)} strides "
-                             f"{t.stride()} on {t.device}")
-    if B > 1 and k2.stride(0) != v2.stride(0):
-        raise ValueError(f"{who}: k2 and v2 must share a row stride, got "
-                         f"{k2.stride(0)} and {v2.stride(0)}")
-    for name, t in (("cos", cos), ("sin", sin)):
-        _mx_check_dense(f"{who}: {name}", t, torch.float32)
-        if t.device != dev or t.dim() != 2 or t.shape[1] != D // 2 \
-                or t.shape[0] < Smax:
-            raise ValueError(f"{who}: {name} {tuple(t.shape)} on {t.device} "
-                             f"must be (>= {Smax}, {D // 2}) on {dev}: the "
-                             f"RoPE table covers the cache")
-    if pos_t.dtype != torch.int64 or pos_t.device != dev \
-            or pos_t.numel() != 1:
-        raise ValueError(f"{who}: pos_t must be one int64 on {dev}, got "
-                         f"{pos_t.dtype} {tuple(pos_t.shape)} on "
-                         f"{pos_t.device}")
-    rep = Hq // Hkv
-    # split-KV workspace (4 splits, shared with decode_attn.hip's merge):
-    # cached-alloc tensors with static shapes, hipGraph-capturable
-    part_o = torch.empty(B * Hkv * 4, rep, D, dtype=torch.float32, device=dev)
-    part_ml = torch.empty(B * Hkv * 4, rep, 2, dtype=torch.float32,
-                          device=dev)
-    out = torch.empty(B, Hq * D, dtype=torch.bfloat16, device=dev)
-    qs = int(q2.stride(0)) if B > 1 else Hq * D
-    kvs = int(k2.stride(0)) if B > 1 else Hkv * D
+                         f"Hkv={Hkv} outside the kernel contract (D = 128)")
+    qs, kvs = _decode_attn_check(who, q2, k2, v2, cos, sin, pos_t, B, Hq, Hkv,
+                                 Smax, dev)
+    part_o, part_ml, out = _decode_attn_workspace(B, Hq, Hkv, dev)
     rc = lib.decode_attn_mx(_ptr(q2), _ptr(k2), _ptr(v2), _ptr(k_payload),
                             _ptr(k_scale), _ptr(v_payload), _ptr(v_scale),
                             _ptr(cos), _ptr(sin), _ptr(pos_t), _ptr(part_o),

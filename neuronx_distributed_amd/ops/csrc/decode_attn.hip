@@ -14,26 +14,17 @@
 //       retires 4 rows/iteration:                                  31 us
 //
 // Phase 1 (decode_attn_part): WG (b, kvh, split s) flash-decodes its
-// pos/SPLIT row chunk, merges its quarter-wave partials in LDS, writes
+// pos/DA_SPLIT row chunk, merges its quarter-wave partials in LDS, writes
 // one fp32 partial (m, l, o[REP][128]) to workspace; split 0 also
 // appends the new K/V row and adds its term.  Phase 2
 // (decode_attn_merge) log-sum-exp-combines the splits -> bf16 out.
 //
-// Layouts (bf16 unless noted): q_lin (B, Hq*D) row-stride qstride,
-// k_lin/v_lin (B, Hkv*D) row-stride kvstride (strided fused-QKV views
-// feed directly); kcache/vcache (B, Hkv, Smax, D); cos/sin (Smax, D/2)
-// fp32; pos_ptr device int64 (hipGraph-replayable); workspace part_o
-// (B*Hkv*SPLIT, REP, D) fp32 + part_ml (..., 2) fp32.  D = 128.
+// Constants, layouts and every phase-1 piece but the walk over the cache
+// are in decode_attn_common.h, shared with decode_attn_mx.hip.
+// kcache/vcache are bf16 (B, Hkv, Smax, D).
 
-#include "common.h"
+#include "decode_attn_common.h"
 #include "mfma.h"
-
-#define DA_D 128
-#define LOG2E 1.4426950408889634f
-
-#define DA_WAVES 4  // 4 waves x 4 quarter-rows = 16 rows in flight per WG
-#define DA_SPLIT 4  // KV-range splits per (batch, kv-head)
-#define DA_NAME decode_attn
 
 template <int REP>
 __global__ void __launch_bounds__(DA_WAVES * 64)
@@ -47,82 +38,46 @@ decode_attn_part(const short* __restrict__ qlin,
                     float* __restrict__ part_o, float* __restrict__ part_ml,
                     int B, int Hq, int Hkv, int Smax, float scale,
                     int qstride, int kvstride) {
-  const int wg = blockIdx.x;
-  const int s = wg % DA_SPLIT;
-  const int pair = wg / DA_SPLIT;
-  const int kvh = pair % Hkv;
-  const int b = pair / Hkv;
-  const int qh0 = kvh * REP;
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int half = (lane >> 4);      // 0..3: which row of the quad
-  const int hl = lane & 15;          // lane within quarter; 8 dims each
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const long pos = *pos_ptr;
-  const long chunk = (pos + DA_SPLIT - 1) / DA_SPLIT;
-  const long r0 = (long)s * chunk;
-  const long r1 = min(pos, r0 + chunk);
+  DaCoord c;
+  da_coord<REP>(c, pos_ptr, Hkv);
+  const int tid = c.tid, hl = c.hl;
 
   __shared__ float qr[REP][DA_D];
   __shared__ float knr[DA_D];
   __shared__ float vn[DA_D];
-  __shared__ float merge_o[4 * DA_WAVES + 1][REP][DA_D];
-  __shared__ float merge_ml[4 * DA_WAVES + 1][REP][2];
+  __shared__ float merge_o[DA_SLOTS + 1][REP][DA_D];
+  __shared__ float merge_ml[DA_SLOTS + 1][REP][2];
 
+  // every split ropes the new k and loads v; only split 0 uses them
   if (tid < 64) {
-    const float c = cosp[pos * (DA_D / 2) + tid];
-    const float sn = sinp[pos * (DA_D / 2) + tid];
-#pragma unroll
-    for (int g = 0; g < REP; ++g) {
-      const long base = (long)b * qstride + (qh0 + g) * DA_D;
-      float x0 = bits2f(qlin[base + tid]);
-      float x1 = bits2f(qlin[base + tid + 64]);
-      qr[g][tid] = x0 * c - x1 * sn;
-      qr[g][tid + 64] = x1 * c + x0 * sn;
-    }
-    {
-      const long base = (long)b * kvstride + kvh * DA_D;
-      float x0 = bits2f(klin[base + tid]);
-      float x1 = bits2f(klin[base + tid + 64]);
-      knr[tid] = x0 * c - x1 * sn;
-      knr[tid + 64] = x1 * c + x0 * sn;
-    }
+    const float cs = cosp[c.pos * (DA_D / 2) + tid];
+    const float sn = sinp[c.pos * (DA_D / 2) + tid];
+    da_rope_q<REP>(qlin, qstride, c, cs, sn, qr);
+    da_rope_pair(klin, (long)c.b * kvstride + c.kvh * DA_D, tid, cs, sn,
+                 knr[tid], knr[tid + 64]);
   } else if (tid < 128) {
     int i = tid - 64;
-    vn[i] = bits2f(vlin[(long)b * kvstride + kvh * DA_D + i]);
-    vn[i + 64] = bits2f(vlin[(long)b * kvstride + kvh * DA_D + i + 64]);
+    vn[i] = bits2f(vlin[(long)c.b * kvstride + c.kvh * DA_D + i]);
+    vn[i + 64] = bits2f(vlin[(long)c.b * kvstride + c.kvh * DA_D + i + 64]);
   }
   __syncthreads();
 
-  if (s == 0 && tid < DA_D) {
-    const long cache_row = (((long)b * Hkv + kvh) * Smax + pos) * DA_D;
+  if (c.s == 0 && tid < DA_D) {
+    const long cache_row = (((long)c.b * Hkv + c.kvh) * Smax + c.pos) * DA_D;
     kcache[cache_row + tid] = f2bits(knr[tid]);
     vcache[cache_row + tid] = f2bits(vn[tid]);
   }
 
-  const short* kc = kcache + ((long)b * Hkv + kvh) * Smax * DA_D;
-  const short* vc = vcache + ((long)b * Hkv + kvh) * Smax * DA_D;
-  const float s2 = scale * LOG2E;
-  // this lane's 8 q dims (per head): dims 8*hl .. 8*hl+7
-  float qv[REP][8];
-#pragma unroll
-  for (int g = 0; g < REP; ++g)
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-      qv[g][j] = qr[g][8 * hl + j];
-
-  float m_run[REP], l_run[REP], ov[REP][8];
-#pragma unroll
-  for (int g = 0; g < REP; ++g) {
-    m_run[g] = -1e30f;
-    l_run[g] = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) ov[g][j] = 0.f;
-  }
+  const short* kc = kcache + ((long)c.b * Hkv + c.kvh) * Smax * DA_D;
+  const short* vc = vcache + ((long)c.b * Hkv + c.kvh) * Smax * DA_D;
+  const float s2 = scale * DA_LOG2E;
+  float qv[REP][8], m_run[REP], l_run[REP], ov[REP][8];
+  da_init_state<REP>(qr, hl, qv, m_run, l_run, ov);
 
   // row quad per wave-iteration: row = base + wid*4 + quarter
-  long r = r0 + 4 * wid + half;
-  const long rstep = 4 * DA_WAVES;
+  const long r1 = c.r1;
+  long r = c.r0 + 4 * c.wid + c.quarter;
+  const long rstep = DA_SLOTS;
   uint4v kp = {0, 0, 0, 0}, vp = {0, 0, 0, 0};
   if (r < r1) {
     kp = *(const uint4v*)(kc + r * DA_D + 8 * hl);
@@ -150,12 +105,7 @@ decode_attn_part(const short* __restrict__ qlin,
 #pragma unroll
       for (int j = 0; j < 8; ++j) part[g] += qv[g][j] * kf[j];
     }
-    // 4-step xor reduce WITHIN each 16-lane quarter (all 4 rows per op)
-#pragma unroll
-    for (int off = 8; off > 0; off >>= 1)
-#pragma unroll
-      for (int g = 0; g < REP; ++g)
-        part[g] += __shfl_xor(part[g], off, 64);
+    da_quarter_reduce<REP>(part);
 #pragma unroll
     for (int g = 0; g < REP; ++g) {
       float sc = part[g] * s2;
@@ -172,68 +122,11 @@ decode_attn_part(const short* __restrict__ qlin,
     vp = vpn;
   }
 
-  // merge: slot = 4*wid + quarter (each quarter-wave is an independent
-  // partial covering dims 8*hl..8*hl+7)
-  const int slot = 4 * wid + half;
-#pragma unroll
-  for (int g = 0; g < REP; ++g) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-      merge_o[slot][g][8 * hl + j] = ov[g][j];
-    if (hl == 0) {
-      merge_ml[slot][g][0] = m_run[g];
-      merge_ml[slot][g][1] = l_run[g];
-    }
-  }
-  const int nslot = 4 * DA_WAVES + (s == 0 ? 1 : 0);
-  if (s == 0 && wid == 0) {
-    float part[REP];
-#pragma unroll
-    for (int g = 0; g < REP; ++g) {
-      part[g] = 0.f;
-#pragma unroll
-      for (int j = 0; j < 8; ++j)
-        part[g] += qv[g][j] * knr[8 * hl + j];
-    }
-#pragma unroll
-    for (int off = 8; off > 0; off >>= 1)
-#pragma unroll
-      for (int g = 0; g < REP; ++g)
-        part[g] += __shfl_xor(part[g], off, 64);
-    // all quarters computed the same new-row score; each writes its dims
-#pragma unroll
-    for (int g = 0; g < REP; ++g) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j)
-        merge_o[4 * DA_WAVES][g][8 * hl + j] = vn[8 * hl + j];
-      if (lane == 0) {
-        merge_ml[4 * DA_WAVES][g][0] = part[g] * s2;
-        merge_ml[4 * DA_WAVES][g][1] = 1.f;
-      }
-    }
-  }
+  da_store_partial<REP>(c, ov, m_run, l_run, merge_o, merge_ml);
+  if (c.s == 0 && c.wid == 0)
+    da_new_row_term<REP>(c, qv, knr, vn, s2, merge_o, merge_ml);
   __syncthreads();
-
-  for (int g = wid; g < REP; g += DA_WAVES) {
-    // lane covers 2 dims like before (64 lanes x 2 = 128)
-    float m_g = -1e30f;
-    for (int w = 0; w < nslot; ++w)
-      m_g = fmaxf(m_g, merge_ml[w][g][0]);
-    float l_g = 0.f, a0 = 0.f, a1 = 0.f;
-    for (int w = 0; w < nslot; ++w) {
-      float sw = __builtin_amdgcn_exp2f(merge_ml[w][g][0] - m_g);
-      l_g += merge_ml[w][g][1] * sw;
-      a0 += merge_o[w][g][2 * lane] * sw;
-      a1 += merge_o[w][g][2 * lane + 1] * sw;
-    }
-    float* po = part_o + ((long)wg * REP + g) * DA_D;
-    po[2 * lane] = a0;
-    po[2 * lane + 1] = a1;
-    if (lane == 0) {
-      part_ml[((long)wg * REP + g) * 2 + 0] = l_g > 0.f ? m_g : -1e30f;
-      part_ml[((long)wg * REP + g) * 2 + 1] = l_g;
-    }
-  }
+  da_merge_store<REP>(c, merge_o, merge_ml, part_o, part_ml);
 }
 
 template <int REP>
@@ -271,46 +164,14 @@ decode_attn_merge(const float* __restrict__ part_o,
   }
 }
 
-extern "C" void decode_attn(const void* qlin, const void* klin,
-                        const void* vlin, void* kcache, void* vcache,
-                        const void* cosp, const void* sinp,
-                        const void* pos_ptr, void* part_o, void* part_ml,
-                        void* outp, int B, int Hq, int Hkv, int Smax,
-                        float scale, int qstride, int kvstride,
-                        hipStream_t stream) {
-  const int rep = Hq / Hkv;
-  dim3 grid1(B * Hkv * DA_SPLIT);
-  dim3 grid2(B * Hkv);
-#define LAUNCH(R)                                                        \
-  do {                                                                   \
-    decode_attn_part<R><<<grid1, DA_WAVES * 64, 0, stream>>>(         \
-        (const short*)qlin, (const short*)klin, (const short*)vlin,      \
-        (short*)kcache, (short*)vcache, (const float*)cosp,              \
-        (const float*)sinp, (const long*)pos_ptr, (float*)part_o,        \
-        (float*)part_ml, B, Hq, Hkv, Smax, scale, qstride, kvstride);    \
-    decode_attn_merge<R><<<grid2, 256, 0, stream>>>(                  \
-        (const float*)part_o, (const float*)part_ml, (short*)outp, B,    \
-        Hq, Hkv);                                                        \
-  } while (0)
-  switch (rep) {
-    case 1: LAUNCH(1); break;
-    case 2: LAUNCH(2); break;
-    case 4: LAUNCH(4); break;
-    case 8: LAUNCH(8); break;
-    default: LAUNCH(1); break;
-  }
-#undef LAUNCH
-}
-
-// Phase 2 on its own, for phase-1 kernels of other cache formats
-// (decode_attn_mx.hip): the fp32 partials carry no trace of the format.
-// Returns non-zero, launching nothing, if the caller's split count is not
-// the one decode_attn_merge was built for or rep is not 1/2/4/8.
+// Phase 2 for every phase-1 kernel (this file's and decode_attn_mx.hip's):
+// the fp32 partials carry no trace of the cache format.  Returns non-zero,
+// launching nothing, unless Hq / Hkv is 1, 2, 4 or 8.
 extern "C" int decode_attn_merge_launch(const void* part_o,
                                         const void* part_ml, void* outp,
-                                        int B, int Hq, int Hkv, int splits,
+                                        int B, int Hq, int Hkv,
                                         hipStream_t stream) {
-  if (splits != DA_SPLIT || B < 1 || Hkv < 1 || Hq % Hkv != 0) return 1;
+  if (B < 1 || Hkv < 1 || Hq % Hkv != 0) return 1;
   dim3 grid2(B * Hkv);
 #define LAUNCH(R)                                                        \
   decode_attn_merge<R><<<grid2, 256, 0, stream>>>(                       \
@@ -325,4 +186,30 @@ extern "C" int decode_attn_merge_launch(const void* part_o,
   }
 #undef LAUNCH
   return 0;
+}
+
+// Returns non-zero, launching nothing, outside da_launch_ok's contract.
+extern "C" int decode_attn(const void* qlin, const void* klin,
+                           const void* vlin, void* kcache, void* vcache,
+                           const void* cosp, const void* sinp,
+                           const void* pos_ptr, void* part_o, void* part_ml,
+                           void* outp, int B, int Hq, int Hkv, int Smax,
+                           float scale, int qstride, int kvstride,
+                           hipStream_t stream) {
+  if (!da_launch_ok(B, Hq, Hkv, Smax, qstride, kvstride)) return 1;
+  dim3 grid1(B * Hkv * DA_SPLIT);
+#define LAUNCH(R)                                                        \
+  decode_attn_part<R><<<grid1, DA_WAVES * 64, 0, stream>>>(              \
+      (const short*)qlin, (const short*)klin, (const short*)vlin,        \
+      (short*)kcache, (short*)vcache, (const float*)cosp,                \
+      (const float*)sinp, (const long*)pos_ptr, (float*)part_o,          \
+      (float*)part_ml, B, Hq, Hkv, Smax, scale, qstride, kvstride)
+  switch (Hq / Hkv) {
+    case 1: LAUNCH(1); break;
+    case 2: LAUNCH(2); break;
+    case 4: LAUNCH(4); break;
+    default: LAUNCH(8); break;
+  }
+#undef LAUNCH
+  return decode_attn_merge_launch(part_o, part_ml, outp, B, Hq, Hkv, stream);
 }

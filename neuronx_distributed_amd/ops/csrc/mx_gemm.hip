@@ -59,21 +59,9 @@ mx_quantize_rows_kernel(const short* __restrict__ x, long row_stride,
 #pragma unroll
   for (int i = 0; i < 4; ++i) v[i] = src[i];
 
-  // the quantizer proper lives in mx_quant.h (shared with mx_skinny.hip)
-  int ab = 0;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) ab = mxq_amax_bits(v[i], ab);
-  const int e = mxq_block_exp(ab);
-  const float inv = mxq_inv_scale(e);
-
+  // the quantizer proper lives in mx_quant.h
   uint4v out[2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    unsigned w0, w1;
-    mxq_cvt8(v[i], inv, w0, w1);
-    out[i >> 1][2 * (i & 1)] = w0;
-    out[i >> 1][2 * (i & 1) + 1] = w1;
-  }
+  const int e = mxq_block32(v, out);
   uint4v* dst = (uint4v*)(q + row * K + 32 * kb);
   dst[0] = out[0];
   dst[1] = out[1];

@@ -1,19 +1,34 @@
-// The MXFP8 (e4m3 + e8m0) activation quantizer, shared by mx_quantize_rows
-// (mx_gemm.hip: one thread per 32-element block) and the fused quantizer of
-// mx_skinny.hip (one lane per 16-element half block, in the MFMA's operand
-// layout).  Both are built from the same four pieces, so the scale rule, the
-// 2^-126 clamp and the cvt_pk_fp8_f32 rounding cannot drift apart:
+// The MXFP8 (e4m3 + e8m0) quantizer and its inverse, in one place so that
+// the scale rule, the 2^-126 clamp and the cvt_pk_fp8_f32 rounding cannot
+// drift apart.  Users:
+//
+//   mx_gemm.hip        mx_quantize_rows_kernel   one thread per 32-block
+//   decode_attn_mx.hip mx_kv_store_kernel        one thread per 32-block
+//                      damx_append_block         the same, from LDS, + dequant
+//                      decode_attn_mx_part       dequant of cache rows
+//   mx_skinny.hip      the fused quantizer: one lane per 16-element half
+//                      block, in the MFMA's operand layout
+//
+// The four pieces:
 //
 //   ab  = mxq_amax_bits(...)   block amax on the bf16 magnitude bits
 //   e   = mxq_block_exp(ab)    smallest e with amax * 2^-e <= 448, clamped
 //   inv = mxq_inv_scale(e)     2^-e, exact
 //   mxq_cvt8(v, inv, w0, w1)   8 bf16 -> 8 e4m3 bytes in memory order
 //
+// mxq_block32 chains them for one whole block held by one thread; the
+// half-block mapping of mx_skinny.hip calls the pieces itself.  The inverse
+// is mxq_scale (e8m0 byte -> float) and mxq_dcvt8 (8 e4m3 bytes -> floats).
+//
 // Bit-identical to pack_mx(*quantize_mx(x, "fp8_e4m3")) of
 // quantization/microscaling.py (tests/test_mx_gemm_gpu.py::test_quantize_*).
 #pragma once
 
 #include "common.h"
+
+typedef unsigned int uint4v __attribute__((ext_vector_type(4)));
+typedef unsigned int uint2v __attribute__((ext_vector_type(2)));
+typedef float f2v __attribute__((ext_vector_type(2)));
 
 // running max of the bf16 magnitude bits (ordered like the values)
 __device__ __forceinline__ int mxq_amax_bits(s8v v, int ab) {
@@ -51,4 +66,43 @@ __device__ __forceinline__ void mxq_cvt8(s8v v, float inv, unsigned& w0,
                                       b, true);
   w0 = (unsigned)a;
   w1 = (unsigned)b;
+}
+
+// One 32-element block held as four s8v: the 32 e4m3 bytes in memory order
+// into out[0..1]; returns the block exponent e (the scale byte is e + 127).
+__device__ __forceinline__ int mxq_block32(const s8v* v, uint4v* out) {
+  int ab = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) ab = mxq_amax_bits(v[i], ab);
+  const int e = mxq_block_exp(ab);
+  const float inv = mxq_inv_scale(e);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    unsigned w0, w1;
+    mxq_cvt8(v[i], inv, w0, w1);
+    out[i >> 1][2 * (i & 1)] = w0;
+    out[i >> 1][2 * (i & 1) + 1] = w1;
+  }
+  return e;
+}
+
+// The inverse.  Scale byte b in 1..254 is 2^(b-127), built as the float with
+// exponent field b; byte 0 (all-zero / negligible block) reads as 0.
+__device__ __forceinline__ float mxq_scale(unsigned b) {
+  union { unsigned u; float f; } c;
+  c.u = b << 23;
+  return c.f;
+}
+
+// 8 e4m3 bytes in memory order -> 8 floats (v_cvt_pk_f32_fp8)
+__device__ __forceinline__ void mxq_dcvt8(uint2v w, float* f) {
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const f2v lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[i], false);
+    const f2v hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[i], true);
+    f[4 * i] = lo[0];
+    f[4 * i + 1] = lo[1];
+    f[4 * i + 2] = hi[0];
+    f[4 * i + 3] = hi[1];
+  }
 }

@@ -496,6 +496,40 @@ def test_guards():
         assert not t.any()
 
 
+def test_guards_bf16():
+    """decode_attn_step makes the same checks as the MX wrapper: each of
+    these raises ValueError and launches nothing."""
+    rep, pos, Smax = 2, 4, 8
+    cos, sin = _rope_table(Smax)
+    kc = torch.zeros(B, HKV, Smax, D, dtype=torch.bfloat16, device="cuda")
+    vc = torch.zeros_like(kc)
+    q2 = torch.ones(B, HKV * rep * D, dtype=torch.bfloat16, device="cuda")
+    kv = torch.ones(B, HKV * D, dtype=torch.bfloat16, device="cuda")
+    wide = torch.ones(B, 2 * HKV * D, dtype=torch.bfloat16, device="cuda")
+    tail = (HKV * rep, HKV, SCALE)
+    with pytest.raises(ValueError):      # GQA rep 3
+        ops.decode_attn_step(
+            torch.ones(B, HKV * 3 * D, dtype=torch.bfloat16, device="cuda"),
+            kv, kv, kc, vc, cos, sin, _pos_t(pos), HKV * 3, HKV, SCALE)
+    with pytest.raises(ValueError):      # q2 of the wrong width
+        ops.decode_attn_step(q2[:, :-D], kv, kv, kc, vc, cos, sin,
+                             _pos_t(pos), *tail)
+    with pytest.raises(ValueError):      # fp32 q2
+        ops.decode_attn_step(q2.float(), kv, kv, kc, vc, cos, sin,
+                             _pos_t(pos), *tail)
+    with pytest.raises(ValueError):      # k2, v2 of different row strides
+        ops.decode_attn_step(q2, wide[:, :HKV * D], kv, kc, vc, cos, sin,
+                             _pos_t(pos), *tail)
+    with pytest.raises(ValueError):      # RoPE table shorter than the cache
+        ops.decode_attn_step(q2, kv, kv, kc, vc, cos[:Smax - 1],
+                             sin[:Smax - 1], _pos_t(pos), *tail)
+    with pytest.raises(ValueError):      # int32 position
+        ops.decode_attn_step(q2, kv, kv, kc, vc, cos, sin,
+                             _pos_t(pos).int(), *tail)
+    torch.cuda.synchronize()
+    assert not kc.any() and not vc.any()     # nothing was appended
+
+
 # ---------------------------------------------------------------------------
 # 8. end to end
 # ---------------------------------------------------------------------------

@@ -214,18 +214,12 @@ def test_flash_attn_strided_bshd_matches_contiguous(B, Hq, Hkv, S):
     assert torch.equal(gv_s.transpose(1, 2), vc.grad), "dv mismatch"
 
 
-@pytest.mark.parametrize("B,Hq,Hkv,pos", [
-    (32, 32, 8, 1023),   # llama3-8b decode shape, batch 32
-    (4, 8, 8, 511),      # MHA
-    (1, 4, 1, 63),       # extreme GQA, tiny batch
-])
-def test_decode_attn_numerics(B, Hq, Hkv, pos):
-    """Fused decode attention (RoPE + cache append + flash-decode + GQA)
-    vs a plain fp32 torch reference over the same cache."""
-    if not ops.decode_attn_available():
-        pytest.skip("decode_attn kernel not built")
+def _decode_attn_case(B, Hq, Hkv, pos, Smax):
+    """Random inputs, one ops.decode_attn_step call, and the plain fp32
+    torch reference over the same cache.  Returns (out, ref, k_new, v_new,
+    caches after the call, caches before it, a re-run closure)."""
     torch.manual_seed(11)
-    D, Smax = 128, pos + 65
+    D = 128
     dev = "cuda"
     cos, sin = ops.precompute_rope_freqs(Smax, D, device=dev)
     kcache = torch.randn(B, Hkv, Smax, D, dtype=torch.bfloat16, device=dev) * 0.5
@@ -240,8 +234,11 @@ def test_decode_attn_numerics(B, Hq, Hkv, pos):
     pos_t = torch.tensor([pos], dtype=torch.int64, device=dev)
     scale = 1.0 / math.sqrt(D)
 
-    out = ops.decode_attn_step(q2, k2, v2, kcache, vcache, cos, sin, pos_t,
-                               Hq, Hkv, scale)
+    def run(kc, vc):
+        return ops.decode_attn_step(q2, k2, v2, kc, vc, cos, sin, pos_t,
+                                    Hq, Hkv, scale)
+
+    out = run(kcache, vcache)
     torch.cuda.synchronize()
 
     # ---- torch fp32 reference -----------------------------------------
@@ -254,20 +251,56 @@ def test_decode_attn_numerics(B, Hq, Hkv, pos):
 
     q = rope(q2.view(B, Hq, D), pos)
     k_new = rope(k2.view(B, Hkv, D), pos)
+    v_new = v2.view(B, Hkv, D).float()
     kc = kc_ref.float()
     vc = vc_ref.float()
     kc[:, :, pos] = k_new
-    vc[:, :, pos] = v2.view(B, Hkv, D).float()
+    vc[:, :, pos] = v_new
     rep = Hq // Hkv
     kx = kc[:, :, : pos + 1].repeat_interleave(rep, dim=1)
     vx = vc[:, :, : pos + 1].repeat_interleave(rep, dim=1)
     att = torch.softmax((q.unsqueeze(2) @ kx.transpose(-1, -2)) * scale, -1)
     ref = (att @ vx).squeeze(2).reshape(B, Hq * D)
+    return out, ref, k_new, v_new, (kcache, vcache), (kc_ref, vc_ref), run
+
+
+@pytest.mark.parametrize("B,Hq,Hkv,pos", [
+    (32, 32, 8, 1023),   # llama3-8b decode shape, batch 32
+    (4, 8, 8, 511),      # MHA
+    (1, 4, 1, 63),       # extreme GQA, tiny batch
+])
+def test_decode_attn_numerics(B, Hq, Hkv, pos):
+    """Fused decode attention (RoPE + cache append + flash-decode + GQA)
+    vs a plain fp32 torch reference over the same cache."""
+    if not ops.decode_attn_available():
+        pytest.skip("decode_attn kernel not built")
+    out, ref, k_new, v_new, (kcache, vcache), _, _ = _decode_attn_case(
+        B, Hq, Hkv, pos, pos + 65)
     _cmp(out, ref, atol=3e-2, name=f"decode_attn B{B} Hq{Hq}")
     # the kernel must also have appended to the cache
     _cmp(kcache[:, :, pos].float(), k_new, atol=2e-2, name="cache k append")
-    _cmp(vcache[:, :, pos].float(), v2.view(B, Hkv, D).float(), atol=1e-3,
-         name="cache v append")
+    _cmp(vcache[:, :, pos].float(), v_new, atol=1e-3, name="cache v append")
+
+
+@pytest.mark.parametrize("pos", [0, 1, 3, 17, 65])
+@pytest.mark.parametrize("rep", [1, 8])
+def test_decode_attn_short_positions(rep, pos):
+    """The bf16 kernel where the split-KV chunks degenerate: every split
+    empty (pos 0), fewer rows than splits (1, 3), a chunk shorter than a
+    16-row wave-iteration (17), one row past a full iteration (65).  Same
+    reference and tolerances as test_decode_attn_numerics; also: no cache
+    row but ``pos`` changes, and a second call gives the same bits."""
+    assert ops.decode_attn_available()
+    B, Hkv = 2, 2
+    out, ref, k_new, v_new, (kcache, vcache), (kc0, vc0), run = \
+        _decode_attn_case(B, Hkv * rep, Hkv, pos, pos + 3)
+    _cmp(out, ref, atol=3e-2, name=f"decode_attn rep{rep} pos{pos}")
+    _cmp(kcache[:, :, pos].float(), k_new, atol=2e-2, name="cache k append")
+    _cmp(vcache[:, :, pos].float(), v_new, atol=1e-3, name="cache v append")
+    for got, before in ((kcache, kc0), (vcache, vc0)):
+        assert torch.equal(got[:, :, :pos], before[:, :, :pos])
+        assert torch.equal(got[:, :, pos + 1:], before[:, :, pos + 1:])
+    assert torch.equal(run(kc0.clone(), vc0.clone()), out)
 
 
 def test_add_rmsnorm_matches_unfused():
