@@ -26,6 +26,10 @@ def main():
     p.add_argument("--prompt-len", type=int, default=64)
     p.add_argument("--new-tokens", type=int, default=64)
     p.add_argument("--spec-len", type=int, default=4)
+    p.add_argument("--fused-verify", action="store_true",
+                   help="verify chunks through the fused multi-token decode "
+                        "attention (device position) instead of rectangular "
+                        "attention over the prefix")
     args = p.parse_args()
 
     os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
@@ -71,13 +75,15 @@ def main():
     t0 = time.perf_counter()
     out, rate = speculative_generate(target, draft, x,
                                      max_new_tokens=args.new_tokens,
-                                     spec_len=args.spec_len)
+                                     spec_len=args.spec_len,
+                                     fused_verify=args.fused_verify)
     t_spec = time.perf_counter() - t0
     assert torch.equal(out, ref), "speculative output diverged"
 
     t0 = time.perf_counter()
     out_m, rate_m = medusa_generate(target, heads, x,
-                                    max_new_tokens=args.new_tokens)
+                                    max_new_tokens=args.new_tokens,
+                                    fused_verify=args.fused_verify)
     t_med = time.perf_counter() - t0
     assert torch.equal(out_m, ref), "medusa output diverged"
 

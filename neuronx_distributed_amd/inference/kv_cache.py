@@ -25,8 +25,10 @@ class KVCache:
 
         ``pos`` may be a device int64 tensor of shape (1,) (hipGraph
         decode): the write becomes index_copy_ and the FULL buffers are
-        returned (attention masks by position — no dynamic shapes)."""
+        returned (attention masks by position — no dynamic shapes).  With
+        S > 1 the rows go to ``pos + arange(S)``."""
         if isinstance(pos, torch.Tensor):
+            pos = _chunk_rows(pos, k_new.shape[2])
             self.k.index_copy_(2, pos, k_new.to(self.k.dtype))
             self.v.index_copy_(2, pos, v_new.to(self.v.dtype))
             return self.k, self.v
@@ -34,6 +36,14 @@ class KVCache:
         self.k[:, :, pos:pos + S] = k_new
         self.v[:, :, pos:pos + S] = v_new
         return self.k[:, :, :pos + S], self.v[:, :, :pos + S]
+
+
+def _chunk_rows(pos: torch.Tensor, S: int) -> torch.Tensor:
+    """Cache row indices of S new tokens at the device position ``pos``:
+    ``pos`` itself for one token, ``pos + arange(S)`` for a chunk."""
+    if S == 1:
+        return pos
+    return pos.reshape(1) + torch.arange(S, device=pos.device)
 
 
 KV_FORMATS = (None, "mxfp8")
@@ -93,6 +103,10 @@ class RollingKVCache(KVCache):
 
     def update(self, k_new: torch.Tensor, v_new: torch.Tensor, pos):
         if isinstance(pos, torch.Tensor):  # decode: one token
+            if k_new.shape[2] != 1:
+                raise NotImplementedError(
+                    "RollingKVCache takes one token per tensor-position "
+                    "update; a multi-token chunk needs a plain cache")
             slot = pos % self.window
             self.k.index_copy_(2, slot, k_new.to(self.k.dtype))
             self.v.index_copy_(2, slot, v_new.to(self.v.dtype))
@@ -179,6 +193,7 @@ class MXKVCache(KVCache):
         """Same signature and modes as :meth:`KVCache.update`; the returned
         K, V are dequantized copies in ``dtype`` (class docstring)."""
         if isinstance(pos, torch.Tensor):
+            pos = _chunk_rows(pos, k_new.shape[2])
             kq, ks = self._quantize(k_new)
             vq, vs = self._quantize(v_new)
             self.k.index_copy_(2, pos, kq)

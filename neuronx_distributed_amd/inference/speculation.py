@@ -22,15 +22,30 @@ def _greedy(logits: torch.Tensor) -> torch.Tensor:
     return logits.argmax(dim=-1)
 
 
+def _chunk_pos(pos: int, n_tokens: int, fused: bool, device):
+    """The position argument of a multi-token forward at ``pos``: a device
+    int64 tensor, which routes attention to the fused chunk step
+    (LlamaAttention._chunk_step), when ``fused`` and the forward is one that
+    step takes (2..8 tokens against a cache that holds rows); else the int."""
+    if fused and pos > 0 and 2 <= n_tokens <= 8:
+        return torch.tensor([pos], dtype=torch.long, device=device)
+    return pos
+
+
 @torch.no_grad()
 def speculative_generate(target, draft, input_ids: torch.Tensor,
                          max_new_tokens: int = 32, spec_len: int = 4,
-                         kv_format=None):
+                         kv_format=None, fused_verify: bool = False):
     """Greedy speculative generation.  target/draft:
     LlamaForCausalLM-compatible; input_ids (B, S).  Returns
     (tokens (B, S+new), acceptance_rate).  ``kv_format``: the cache format
-    of both models (build_kv_caches)."""
+    of both models (build_kv_caches).  ``fused_verify``: run the target's
+    verify chunk and the draft's two-token step with a device position, i.e.
+    through the fused multi-token decode attention (ops.chunk_attn_step /
+    ops.chunk_attn_mx_step on GPU) instead of rectangular attention over the
+    prefix; chunks of more than 8 tokens keep the default path."""
     B, S = input_ids.shape
+    dev = input_ids.device
 
     def make_caches(model):
         cfg = model.config
@@ -68,7 +83,7 @@ def speculative_generate(target, draft, input_ids: torch.Tensor,
         proposals = []
         cur = tok
         dl = draft(torch.stack([d_prev, cur], 1), kv_caches=d_caches,
-                   pos_offset=pos - 1)
+                   pos_offset=_chunk_pos(pos - 1, 2, fused_verify, dev))
         proposals.append(_greedy(dl[:, -1, :]))
         for i in range(1, k):
             dl = draft(proposals[-1].unsqueeze(1), kv_caches=d_caches,
@@ -78,7 +93,8 @@ def speculative_generate(target, draft, input_ids: torch.Tensor,
 
         # ---- target verifies the chunk in one forward ----------------
         chunk = torch.cat([tok.unsqueeze(1), dmat], dim=1)  # (B, k+1)
-        tl = target(chunk, kv_caches=t_caches, pos_offset=pos)
+        tl = target(chunk, kv_caches=t_caches,
+                    pos_offset=_chunk_pos(pos, k + 1, fused_verify, dev))
         tmat = _greedy(tl)  # (B, k+1): target choice AFTER each prefix
 
         # longest agreeing prefix (whole batch must agree to advance a
@@ -105,13 +121,15 @@ def speculative_generate(target, draft, input_ids: torch.Tensor,
 
 @torch.no_grad()
 def medusa_generate(target, medusa_heads, input_ids: torch.Tensor,
-                    max_new_tokens: int = 32, kv_format=None):
+                    max_new_tokens: int = 32, kv_format=None,
+                    fused_verify: bool = False):
     """Medusa-style speculation: ``medusa_heads`` (iterable of
     utils.medusa_utils.MedusaHead, head i predicting the token at offset
     i+2) propose a chain from the LAST HIDDEN STATE in one shot — no
     autoregressive draft model — and the target verifies the chunk exactly
     like :func:`speculative_generate`.  Greedy output is identical to
-    plain generation."""
+    plain generation.  ``fused_verify``: as in :func:`speculative_generate`,
+    for the verify chunk."""
     from ..utils.sampling import Sampler
 
     sampler = Sampler(do_sample=False)
@@ -143,7 +161,10 @@ def medusa_generate(target, medusa_heads, input_ids: torch.Tensor,
         props = [sampler(heads[i](h_last)) for i in range(kk)]
         dmat = torch.stack(props, dim=1)  # (B, kk)
         chunk = torch.cat([tok.unsqueeze(1), dmat], dim=1)
-        hidden = target.model(chunk, pos_offset=pos, kv_caches=caches)
+        hidden = target.model(
+            chunk, kv_caches=caches,
+            pos_offset=_chunk_pos(pos, kk + 1, fused_verify,
+                                  input_ids.device))
         tl = target.lm_head(hidden)
         tmat = torch.stack([sampler(tl[:, i, :])
                             for i in range(kk + 1)], dim=1)

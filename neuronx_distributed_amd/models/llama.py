@@ -205,10 +205,19 @@ class LlamaAttention(nn.Module):
         k = k.reshape(B, S, self.num_kv_local, self.head_dim)
         v = v.reshape(B, S, self.num_kv_local, self.head_dim)
         if isinstance(pos_offset, torch.Tensor):
-            # hipGraph-capturable decode: device-tensor position, S == 1,
+            # hipGraph-capturable decode: device-tensor position, S == 1
+            # (or a chunk of 2..8 tokens: speculative verification),
             # full-cache masked attention (no dynamic shapes)
-            return self._decode_step(q, k, v, cos, sin, pos_offset,
-                                     kv_cache, sp)
+            if S == 1:
+                return self._decode_step(q, k, v, cos, sin, pos_offset,
+                                         kv_cache, sp)
+            if not 2 <= S <= 8:
+                raise ValueError(
+                    f"a device-tensor position takes 1..8 tokens per "
+                    f"forward, got {S}; use an int position for a longer "
+                    f"chunk")
+            return self._chunk_step(q, k, v, cos, sin, pos_offset, kv_cache,
+                                    sp)
         q, k = ops.apply_rotary_pos_emb(q, k, cos, sin, pos_offset)
 
         # (B,S,h,D) -> (B,h,S,D)
@@ -316,6 +325,91 @@ class LlamaAttention(nn.Module):
         probs = torch.softmax(scores, dim=-1)
         out = probs.to(q.dtype) @ V  # (B,Hkv,rep,D)
         out = out.reshape(B, 1, self.num_heads_local * self.head_dim)
+        if sp:
+            out = out.transpose(0, 1)
+        return self.o_proj(out)
+
+    def _chunk_step(self, q, k, v, cos, sin, pos_t, kv_cache, sp):
+        """S = 2..8 new tokens at the device position ``pos_t``: token t is
+        roped at pos + t, written to cache row pos + t and attends rows
+        [0, pos + t].  Like :meth:`_decode_step` nothing depends on the host
+        knowing the position.
+
+        On GPU with D=128 this is ops.chunk_attn_step (plain bf16 KVCache)
+        or ops.chunk_attn_mx_step (MXKVCache); any other cache, the CPU and
+        odd shapes take the torch chain below (the reference)."""
+        from ..inference.kv_cache import KVCache, MXKVCache
+
+        B, S = q.shape[0], q.shape[1]
+        rep = self.num_heads_local // self.num_kv_local
+        scale = 1.0 / math.sqrt(self.head_dim)
+        fusable = (q.is_cuda and self.head_dim == 128 and rep in (1, 2, 4, 8)
+                   and q.dtype == torch.bfloat16
+                   and self.sliding_window is None)
+        fused_bf16 = (fusable and type(kv_cache) is KVCache
+                      and kv_cache.k.is_cuda
+                      and kv_cache.k.dtype == torch.bfloat16
+                      and ops.chunk_attn_available())
+        fused_mx = (fusable and type(kv_cache) is MXKVCache
+                    and kv_cache.k.is_cuda
+                    and ops.chunk_attn_mx_available())
+        if fused_bf16 or fused_mx:
+            def _flat(t):
+                # (B,S,h,D) -> (B,S,h*D) as a VIEW of a fused-QKV slice where
+                # its strides allow (the kernels take row strides)
+                f = t.reshape(B, S, -1)
+                ok = (f.stride(2) == 1 and f.stride(1) >= f.shape[2]
+                      and f.stride(0) % 8 == 0 and f.stride(1) % 8 == 0
+                      and f.data_ptr() % 16 == 0)
+                return f if ok else f.contiguous()
+
+            q3, k3, v3 = _flat(q), _flat(k), _flat(v)
+            if k3.stride() != v3.stride():
+                k3, v3 = k3.contiguous(), v3.contiguous()
+            tail = (cos, sin, pos_t.reshape(1), self.num_heads_local,
+                    self.num_kv_local, scale)
+            if fused_mx:
+                out = ops.chunk_attn_mx_step(
+                    q3, k3, v3, kv_cache.k, kv_cache.k_scale, kv_cache.v,
+                    kv_cache.v_scale, *tail)
+            else:
+                out = ops.chunk_attn_step(q3, k3, v3, kv_cache.k, kv_cache.v,
+                                          *tail)
+            if sp:
+                out = out.transpose(0, 1)
+            return self.o_proj(out)
+        half = self.head_dim // 2
+        tpos = pos_t.reshape(1) + torch.arange(S, device=q.device)  # (S,)
+        c = cos.index_select(0, tpos).view(1, S, 1, half)
+        s = sin.index_select(0, tpos).view(1, S, 1, half)
+
+        def rope(x):
+            x0 = x[..., :half].float()
+            x1 = x[..., half:].float()
+            return torch.cat([x0 * c - x1 * s, x1 * c + x0 * s],
+                             dim=-1).to(x.dtype)
+
+        q = rope(q).transpose(1, 2)  # (B,h,S,D)
+        k = rope(k).transpose(1, 2)
+        v = v.transpose(1, 2)
+        K, V = kv_cache.update(k, v, pos_t)  # FULL (B,Hkv,Smax,D) buffers
+        if K.dtype != q.dtype:  # a cache kept in another dtype than the model
+            K, V = K.to(q.dtype), V.to(q.dtype)
+        Smax = K.shape[2]
+        # (B,Hkv,rep*S,D) against the cache -> (B,Hkv,rep,S,Smax)
+        qg = q.reshape(B, self.num_kv_local, rep * S, self.head_dim)
+        scores = (qg @ K.transpose(-1, -2)).float() * scale
+        scores = scores.view(B, self.num_kv_local, rep, S, Smax)
+        idx = torch.arange(Smax, device=q.device)
+        invalid = idx.view(1, Smax) > tpos.view(S, 1)  # (S, Smax)
+        if self.sliding_window is not None:
+            invalid = invalid | (idx.view(1, Smax)
+                                 <= tpos.view(S, 1) - self.sliding_window)
+        scores = scores.masked_fill(invalid, float("-inf"))
+        probs = torch.softmax(scores, dim=-1).to(q.dtype)
+        out = probs.view(B, self.num_kv_local, rep * S, Smax) @ V
+        out = out.view(B, self.num_heads_local, S, self.head_dim)
+        out = out.transpose(1, 2).reshape(B, S, -1)
         if sp:
             out = out.transpose(0, 1)
         return self.o_proj(out)

@@ -1412,3 +1412,163 @@ def mx_kv_store(k: torch.Tensor, v: torch.Tensor, k_payload: torch.Tensor,
         raise ValueError(f"mx_kv_store rejected k {tuple(k.shape)} strides "
                          f"{k.stride()} at pos {pos}, cache "
                          f"{tuple(k_payload.shape)}")
+
+
+# ---------------------------------------------------------------------------
+# Fused multi-token decode attention (csrc/chunk_attn.hip): T = 2..8 new
+# tokens against the cache from a device position (speculative verification,
+# chunked prefill)
+# ---------------------------------------------------------------------------
+
+_CA_TMIN, _CA_TMAX = 2, 8   # CA_TMIN / CA_TMAX of csrc/chunk_attn.hip
+
+
+def chunk_attn_available() -> bool:
+    lib = _load()
+    return lib is not None and hasattr(lib, "chunk_attn")
+
+
+def chunk_attn_mx_available() -> bool:
+    lib = _load()
+    return lib is not None and hasattr(lib, "chunk_attn_mx")
+
+
+def _chunk_attn_check(who, q3, k3, v3, cos, sin, pos_t, B, Hq, Hkv, Smax,
+                      dev):
+    """Everything but the cache, for both chunk kernels.  Returns T and the
+    element strides (q batch, q token, kv batch, kv token)."""
+    D = _DA_D
+    if Hkv < 1 or Hq % Hkv or Hq // Hkv not in (1, 2, 4, 8):
+        raise ValueError(f"{who}: Hq={Hq}, Hkv={Hkv} outside the kernel "
+                         f"contract (GQA rep 1/2/4/8)")
+    if q3.dim() != 3 or not _CA_TMIN <= q3.shape[1] <= _CA_TMAX:
+        raise ValueError(f"{who}: q3 {tuple(q3.shape)} must be (B, T, Hq*128) "
+                         f"with {_CA_TMIN} <= T <= {_CA_TMAX}")
+    T = q3.shape[1]
+    if Smax < T:
+        raise ValueError(f"{who}: a cache of {Smax} rows cannot take {T} "
+                         f"tokens")
+    for name, t, width in (("q3", q3, Hq * D), ("k3", k3, Hkv * D),
+                           ("v3", v3, Hkv * D)):
+        if t.dtype != torch.bfloat16 or t.device != dev or t.dim() != 3 \
+                or tuple(t.shape) != (B, T, width) or t.stride(2) != 1 \
+                or t.stride(1) < width or t.data_ptr() % 16 \
+                or t.stride(0) % 8 or t.stride(1) % 8:
+            raise ValueError(f"{who}: {name} must be a 16-byte aligned bf16 "
+                             f"({B}, {T}, {width}) tensor on {dev} with a "
+                             f"dense last dim and row strides that hold a "
+                             f"row, got {t.dtype} {tuple(t.shape)} strides "
+                             f"{t.stride()} on {t.device}")
+    if k3.stride() != v3.stride():
+        raise ValueError(f"{who}: k3 and v3 must share their strides, got "
+                         f"{k3.stride()} and {v3.stride()}")
+    for name, t in (("cos", cos), ("sin", sin)):
+        _mx_check_dense(f"{who}: {name}", t, torch.float32)
+        if t.device != dev or t.dim() != 2 or t.shape[1] != D // 2 \
+                or t.shape[0] < Smax or t.data_ptr() % 16:
+            raise ValueError(f"{who}: {name} {tuple(t.shape)} on {t.device} "
+                             f"must be (>= {Smax}, {D // 2}) on {dev}: the "
+                             f"RoPE table covers the cache")
+    if pos_t.dtype != torch.int64 or pos_t.device != dev \
+            or pos_t.numel() != 1:
+        raise ValueError(f"{who}: pos_t must be one int64 on {dev}, got "
+                         f"{pos_t.dtype} {tuple(pos_t.shape)} on "
+                         f"{pos_t.device}")
+    return T, (int(q3.stride(0)), int(q3.stride(1)), int(k3.stride(0)),
+               int(k3.stride(1)))
+
+
+def _chunk_attn_workspace(B, T, Hq, Hkv, dev):
+    """(part_o, part_ml, out); static shapes from the caching allocator, so
+    the three launches are hipGraph-capturable."""
+    R = Hq // Hkv * T
+    part_o = torch.empty(B * Hkv * _DA_SPLIT, R, _DA_D, dtype=torch.float32,
+                         device=dev)
+    part_ml = torch.empty(B * Hkv * _DA_SPLIT, R, 2, dtype=torch.float32,
+                          device=dev)
+    out = torch.empty(B, T, Hq * _DA_D, dtype=torch.bfloat16, device=dev)
+    return part_o, part_ml, out
+
+
+def chunk_attn_step(q3: torch.Tensor, k3: torch.Tensor, v3: torch.Tensor,
+                    kcache: torch.Tensor, vcache: torch.Tensor,
+                    cos: torch.Tensor, sin: torch.Tensor,
+                    pos_t: torch.Tensor, Hq: int, Hkv: int,
+                    scale: float) -> torch.Tensor:
+    """The multi-token sibling of :func:`decode_attn_step`: T = 2..8 new
+    tokens per sequence.  q3 (B, T, Hq*128), k3/v3 (B, T, Hkv*128) bf16
+    pre-rope (row-strided views with a dense last dim are fine);
+    kcache/vcache bf16 (B, Hkv, Smax, 128); cos/sin (>= Smax, 64) fp32;
+    ``pos_t`` one device int64 -> out (B, T, Hq*128).
+
+    Token t is roped at position pos + t, its K/V row is stored at cache row
+    pos + t (rows at or beyond Smax are not written) and it attends cache
+    rows [0, pos + t] as stored.  Three launches on the current stream, no
+    host sync: hipGraph-capturable.  A wrong dtype or shape raises
+    ValueError and launches nothing."""
+    lib = _require_lib()
+    who = "chunk_attn_step"
+    if not chunk_attn_available():
+        raise RuntimeError("nxd_ops library has no chunk_attn — rebuild")
+    for name, t in (("kcache", kcache), ("vcache", vcache)):
+        if t.dtype != torch.bfloat16 or t.dim() != 4 \
+                or t.shape[-1] != _DA_D or not t.is_cuda \
+                or not t.is_contiguous():
+            raise ValueError(f"{who}: {name} must be a contiguous bf16 "
+                             f"(B, Hkv, Smax, 128) GPU cache, got {t.dtype} "
+                             f"{tuple(t.shape)} on {t.device}")
+    if vcache.shape != kcache.shape or vcache.device != kcache.device \
+            or kcache.shape[1] != Hkv or min(kcache.shape) < 1:
+        raise ValueError(f"{who}: kcache {tuple(kcache.shape)} and vcache "
+                         f"{tuple(vcache.shape)} must be one non-empty shape "
+                         f"on one GPU with Hkv={Hkv} heads")
+    B, _, Smax, _ = kcache.shape
+    dev = kcache.device
+    T, st = _chunk_attn_check(who, q3, k3, v3, cos, sin, pos_t, B, Hq, Hkv,
+                              Smax, dev)
+    part_o, part_ml, out = _chunk_attn_workspace(B, T, Hq, Hkv, dev)
+    rc = lib.chunk_attn(_ptr(q3), _ptr(k3), _ptr(v3), _ptr(kcache),
+                        _ptr(vcache), _ptr(cos), _ptr(sin), _ptr(pos_t),
+                        _ptr(part_o), _ptr(part_ml), _ptr(out), B, T, Hq, Hkv,
+                        Smax, ctypes.c_float(scale),
+                        *(ctypes.c_long(s) for s in st), _stream())
+    if rc != 0:
+        raise ValueError(f"chunk_attn rejected B={B}, T={T}, Hq={Hq}, "
+                         f"Hkv={Hkv}, Smax={Smax}, strides {st}")
+    return out
+
+
+def chunk_attn_mx_step(q3: torch.Tensor, k3: torch.Tensor, v3: torch.Tensor,
+                       k_payload: torch.Tensor, k_scale: torch.Tensor,
+                       v_payload: torch.Tensor, v_scale: torch.Tensor,
+                       cos: torch.Tensor, sin: torch.Tensor,
+                       pos_t: torch.Tensor, Hq: int, Hkv: int,
+                       scale: float) -> torch.Tensor:
+    """:func:`chunk_attn_step` over an MXFP8 cache (``MXKVCache`` buffers).
+    The T new K (after RoPE) and V rows are stored as
+    ``pack_mx(quantize_mx(row))`` and the output attends to the cache as
+    stored, the new rows included."""
+    lib = _require_lib()
+    who = "chunk_attn_mx_step"
+    if not chunk_attn_mx_available():
+        raise RuntimeError("nxd_ops library has no chunk_attn_mx — rebuild")
+    B, Hkv_c, Smax, D = _mxkv_check_cache(who, k_payload, k_scale, v_payload,
+                                          v_scale)
+    dev = k_payload.device
+    if D != _DA_D or Hkv_c != Hkv or not k_payload.is_cuda:
+        raise ValueError(f"{who}: cache {tuple(k_payload.shape)} on {dev} "
+                         f"with Hkv={Hkv} outside the kernel contract "
+                         f"(D = 128, GPU)")
+    T, st = _chunk_attn_check(who, q3, k3, v3, cos, sin, pos_t, B, Hq, Hkv,
+                              Smax, dev)
+    part_o, part_ml, out = _chunk_attn_workspace(B, T, Hq, Hkv, dev)
+    rc = lib.chunk_attn_mx(_ptr(q3), _ptr(k3), _ptr(v3), _ptr(k_payload),
+                           _ptr(k_scale), _ptr(v_payload), _ptr(v_scale),
+                           _ptr(cos), _ptr(sin), _ptr(pos_t), _ptr(part_o),
+                           _ptr(part_ml), _ptr(out), B, T, Hq, Hkv, Smax,
+                           ctypes.c_float(scale),
+                           *(ctypes.c_long(s) for s in st), _stream())
+    if rc != 0:
+        raise ValueError(f"chunk_attn_mx rejected B={B}, T={T}, Hq={Hq}, "
+                         f"Hkv={Hkv}, Smax={Smax}, strides {st}")
+    return out

@@ -6,6 +6,8 @@
 //   decode_attn_mx.hip mx_kv_store_kernel        one thread per 32-block
 //                      damx_append_block         the same, from LDS, + dequant
 //                      decode_attn_mx_part       dequant of cache rows
+//   chunk_attn.hip     chunk_attn_append         one thread per 32-block
+//                      chunk_attn_part           dequant of a tile into LDS
 //   mx_skinny.hip      the fused quantizer: one lane per 16-element half
 //                      block, in the MFMA's operand layout
 //

@@ -1,0 +1,711 @@
+"""GPU checks of the fused multi-token decode attention
+(ops/csrc/chunk_attn.hip: ops.chunk_attn_step for the bf16 cache,
+ops.chunk_attn_mx_step for the MXFP8 cache), T = 2..8 new tokens at a device
+position.  Every reference is attention over the cache AS STORED after the
+call: the kernels append first and read every row, the new ones included,
+from the cache.
+
+* row addressing, exact ("one-hot"): token t's query is 16 on dims
+  [16t, 16t+16) and its target row's K is 8 there, log2-score
+  16*128/sqrt(128)*log2 e ~ 261 against 0 for every other row, so the output
+  is bit-equal to the target row's (dequantized) V; targets differ per token
+  and per (b, kvh) pair and sweep every row 0..pos+T-1,
+* causality and stale rows: a hot NEW row is seen by exactly the tokens at or
+  after it; rows at or beyond pos+T filled with NaN bits change nothing,
+* the K dim map over all 128 dims in both MFMA query row blocks,
+* random numerics against fp64 under a bound measured in the same run from
+  the single-token kernels run T times, the appended rows, the end-of-cache
+  guard, determinism, hipGraph replay, the Python guards, and the model /
+  speculative_generate level.
+
+Measured on MI355X over the 208 cases (4 reps x 4 T x 13 positions) of each
+format in test_random_numerics, max |out - fp64 reference|:
+  bf16:  chunk kernel 5.185e-3, T single-token steps 4.037e-3 (both at pos 0:
+         the rounding of an output near 1 to bf16), worst ratio of one case
+         1.805 (rep 4, T 3, pos 257: 4.399e-4 against 2.438e-4)
+  mxfp8: chunk kernel 5.405e-3, T single-token steps 3.905e-3, worst ratio of
+         one case 1.716 (rep 8, T 3, pos 257: 4.182e-4 against 2.437e-4)
+The MFMA path rounds P and the roped q to bf16, which the VALU kernels do
+not.  ALLOWED_RATIO = 3.61 is twice the worst ratio measured, as room for
+other seeds; the 3e-2 cap of test_ops_gpu.py::test_decode_attn_numerics holds
+on top of it.  Model level (test_model_chunk_matches_reference): max logit
+difference 1.2e-2 at logits up to 1.6 for the bf16 cache.
+"""
+
+import functools
+import math
+import os
+
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+from neuronx_distributed_amd import ops
+from neuronx_distributed_amd.quantization.microscaling import (
+    dequantize_mx, pack_mx, quantize_mx, unpack_mx)
+
+FMT = "fp8_e4m3"
+D = 128
+B, HKV = 2, 2
+NPAIR = B * HKV
+REPS = (1, 2, 4, 8)
+TS = (2, 3, 5, 8)
+POS = (0, 1, 30, 31, 32, 33, 63, 64, 65, 127, 128, 129, 257)
+FORMATS = ("bf16", "mxfp8")
+SCALE = 1.0 / math.sqrt(D)
+ATOL_CAP = 3e-2          # test_ops_gpu.py::test_decode_attn_numerics
+ALLOWED_RATIO = 3.61     # twice the worst measured ratio, 1.805 (docstring)
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _require_lib():
+    assert torch.cuda.is_available()
+    from neuronx_distributed_amd.ops import build as _build
+
+    _build.build()
+    assert ops.is_available(), ops._LIB_ERR
+    assert ops.chunk_attn_available() and ops.chunk_attn_mx_available()
+    assert ops.decode_attn_available() and ops.decode_attn_mx_available()
+
+
+def _packed(x):
+    return pack_mx(*quantize_mx(x, FMT), FMT)
+
+
+def _deq64(payload, scale):
+    q, e = unpack_mx(payload, scale, FMT)
+    return q.double() * torch.exp2(e.double()).repeat_interleave(32, dim=-1)
+
+
+@functools.lru_cache(maxsize=None)
+def _identity_table(n):
+    return (torch.ones(n, D // 2, device="cuda"),
+            torch.zeros(n, D // 2, device="cuda"))
+
+
+@functools.lru_cache(maxsize=None)
+def _rope_table(n):
+    return ops.precompute_rope_freqs(n, D, device="cuda")
+
+
+def _pos_t(pos):
+    return torch.tensor([pos], dtype=torch.int64, device="cuda")
+
+
+def _make_cache(fmt, K, V):
+    """float K, V (nb, nh, Smax, D) on the CPU -> the format's GPU buffers
+    (k, v) or (k_payload, k_scale, v_payload, v_scale)."""
+    if fmt == "bf16":
+        return K.bfloat16().cuda(), V.bfloat16().cuda()
+    kp, ks = _packed(K)
+    vp, vs = _packed(V)
+    return kp.cuda(), ks.cuda(), vp.cuda(), vs.cuda()
+
+
+def _kv64(fmt, cache):
+    """The cache as stored, in fp64: (K, V)."""
+    if fmt == "bf16":
+        return cache[0].double(), cache[1].double()
+    return _deq64(cache[0], cache[1]), _deq64(cache[2], cache[3])
+
+
+def _v_stored(fmt, cache):
+    """V as stored, in bf16 (e4m3 times a power of two is exact there)."""
+    if fmt == "bf16":
+        return cache[1]
+    return dequantize_mx(*unpack_mx(cache[2], cache[3], FMT),
+                         dtype=torch.bfloat16)
+
+
+def _call(fmt, q3, k3, v3, cache, table, pos_t, rep):
+    nh = cache[0].shape[1]
+    fn = ops.chunk_attn_step if fmt == "bf16" else ops.chunk_attn_mx_step
+    if not isinstance(pos_t, torch.Tensor):
+        pos_t = _pos_t(pos_t)
+    return fn(q3, k3, v3, *cache, *table, pos_t, nh * rep, nh, SCALE)
+
+
+def _grid(nb, nh, S, seed=0):
+    """(nb, nh, S, D) floats on the e4m3 grid, |x| <= 1, with a different
+    power-of-two scale per (pair, row, block): both formats hold them
+    exactly."""
+    pair = torch.arange(nb * nh).reshape(nb, nh, 1, 1)
+    r = torch.arange(S).reshape(1, 1, S, 1)
+    d = torch.arange(D).reshape(1, 1, 1, D)
+    v = ((3 * r + 5 * d + 7 * pair + seed) % 17 - 8).float()
+    e = ((r + 2 * (d // 32) + pair + seed) % 4 - 6).float()
+    return v * torch.exp2(e)
+
+
+def _to3(x):
+    """(nb, nh, T, D) -> the kernels' (nb, T, nh * D) bf16 on the GPU."""
+    nb, nh, T, _ = x.shape
+    return x.transpose(1, 2).reshape(nb, T, nh * D).bfloat16().cuda()
+
+
+def _block_q(nb, nh, rep, T):
+    """q3: token t is 16 on dims [16t, 16t + 16) in every head."""
+    q = torch.zeros(nb, T, nh * rep, D)
+    for t in range(T):
+        q[:, t, :, 16 * t:16 * t + 16] = 16.0
+    return q.reshape(nb, T, nh * rep * D).bfloat16().cuda()
+
+
+def _mark_k(nb, nh, Smax, targets):
+    """K (nb, nh, Smax, D): row targets[i][t] of pair i is 8 on token t's
+    dims."""
+    K = torch.zeros(nb * nh, Smax, D)
+    for i, row in enumerate(targets):
+        for t, r in enumerate(row):
+            K[i, r, 16 * t:16 * t + 16] = 8.0
+    return K.reshape(nb, nh, Smax, D)
+
+
+# ---------------------------------------------------------------------------
+# 1. row addressing, exact
+# ---------------------------------------------------------------------------
+
+def _one_hot_call(fmt, rep, T, pos, Smax, targets, V):
+    K = _mark_k(B, HKV, Smax, targets)
+    k3, v3 = _to3(K[:, :, pos:pos + T]), _to3(V[:, :, pos:pos + T])
+    K0, V0 = K.clone(), V.clone()
+    K0[:, :, pos:] = 0
+    V0[:, :, pos:] = 0
+    cache = _make_cache(fmt, K0, V0)
+    out = _call(fmt, _block_q(B, HKV, rep, T), k3, v3, cache,
+                _identity_table(Smax), pos, rep)
+    vd = _v_stored(fmt, cache)
+    # the appended V rows are the inputs, exactly (grid values)
+    assert torch.equal(vd[:, :, pos:pos + T], V[:, :, pos:pos + T]
+                       .bfloat16().cuda())
+    idx = torch.tensor(targets).reshape(B, HKV, T, 1).expand(B, HKV, T, D)
+    want = vd.gather(2, idx.cuda())                       # (B, HKV, T, D)
+    want = want.permute(0, 2, 1, 3).unsqueeze(3).expand(B, T, HKV, rep, D)
+    got = out.view(B, T, HKV, rep, D)
+    assert torch.equal(got, want), (
+        f"{fmt} rep {rep} T {T} pos {pos} targets {targets}: "
+        f"{(got != want).any(-1).nonzero()[:8].tolist()}")
+
+
+@pytest.mark.parametrize("T", TS)
+@pytest.mark.parametrize("rep", REPS)
+@pytest.mark.parametrize("fmt", FORMATS)
+def test_one_hot(fmt, rep, T, pos_list=POS):
+    for pos in pos_list:
+        Smax = pos + T + 2
+        V = _grid(B, HKV, Smax, seed=pos)
+        n = pos + T
+        # every row 0..n-1 in turn, slot (pair i, token t) clamped to the
+        # rows token t may see
+        for base in range(0, n, NPAIR * T):
+            targets = [[min(base + i * T + t, pos + t) for t in range(T)]
+                       for i in range(NPAIR)]
+            _one_hot_call(fmt, rep, T, pos, Smax, targets, V)
+        # the new rows: token t on new row min(t, j + i) for every j
+        for j in range(0, T, NPAIR):
+            targets = [[pos + min(t, j + i) for t in range(T)]
+                       for i in range(NPAIR)]
+            _one_hot_call(fmt, rep, T, pos, Smax, targets, V)
+
+
+# ---------------------------------------------------------------------------
+# 2. causality and stale rows
+# ---------------------------------------------------------------------------
+
+@pytest.mark.parametrize("pos", (0, 31, 33, 129))
+@pytest.mark.parametrize("rep,T", [(1, 2), (2, 5), (4, 8), (8, 3), (8, 8)])
+@pytest.mark.parametrize("fmt", FORMATS)
+def test_hot_new_row_is_causal(fmt, rep, T, pos):
+    """The hot K row is the new row pos + j (8 on every token's dims).
+    Tokens t >= j return V[pos + j] exactly.  Tokens t < j score 0 on every
+    row they may see and must return the plain mean of V rows [0, pos + t];
+    V rows pos + j.. are 2^14, so one leaked row moves the mean by far more
+    than the bound: |V| <= 1 on the rows that count, the output's bf16
+    rounding is <= 2^-9, fp32 accumulation over < 300 rows far less: 2^-8."""
+    Smax = pos + T + 2
+    for j in range(T):
+        V = _grid(B, HKV, Smax, seed=j)
+        V[:, :, pos + j:] = 2.0 ** 14
+        K = torch.zeros(B, HKV, Smax, D)
+        K[:, :, pos + j, :16 * T] = 8.0
+        K0, V0 = K.clone(), V.clone()
+        K0[:, :, pos:] = 0
+        V0[:, :, pos:] = 0
+        cache = _make_cache(fmt, K0, V0)
+        out = _call(fmt, _block_q(B, HKV, rep, T), _to3(K[:, :, pos:pos + T]),
+                    _to3(V[:, :, pos:pos + T]), cache, _identity_table(Smax),
+                    pos, rep).view(B, T, HKV, rep, D)
+        v64 = _kv64(fmt, cache)[1]
+        for t in range(T):
+            if t >= j:
+                want = v64[:, :, pos + j].bfloat16()
+                assert torch.equal(out[:, t],
+                                   want.unsqueeze(2).expand(B, HKV, rep, D)), \
+                    (fmt, rep, T, pos, j, t)
+            else:
+                want = v64[:, :, :pos + t + 1].mean(2)
+                err = (out[:, t].double() - want.unsqueeze(2)).abs().max()
+                assert err <= 2.0 ** -8, (fmt, rep, T, pos, j, t, err.item())
+
+
+def _random_case(fmt, rep, T, pos, Smax, seed, nb=B, nh=HKV):
+    g = torch.Generator().manual_seed(seed)
+    rnd = lambda *s: torch.randn(*s, generator=g) * 0.5   # noqa: E731
+    K, V = rnd(nb, nh, Smax, D), rnd(nb, nh, Smax, D)
+    K[:, :, pos:] = 0
+    V[:, :, pos:] = 0
+    cache = _make_cache(fmt, K, V)
+    q3 = rnd(nb, T, nh * rep * D).bfloat16().cuda()
+    k3 = rnd(nb, T, nh * D).bfloat16().cuda()
+    v3 = rnd(nb, T, nh * D).bfloat16().cuda()
+    return cache, q3, k3, v3
+
+
+@pytest.mark.parametrize("pos", (0, 30, 64, 129))
+@pytest.mark.parametrize("rep,T", [(1, 3), (4, 5), (8, 8)])
+@pytest.mark.parametrize("fmt", FORMATS)
+def test_nan_rows_beyond_chunk_change_nothing(fmt, rep, T, pos):
+    """Rows at or beyond pos + T hold NaN bits (bf16 0x7FC0; MX payload 0x7F
+    with scale 0xFF): the rest of the last tile and two more tiles.  Outputs
+    are finite and bit-equal to those of the same call with zeros there."""
+    Smax = pos + T + 70
+    table = _rope_table(Smax)
+    cache, q3, k3, v3 = _random_case(fmt, rep, T, pos, Smax, 7 + pos)
+    dirty = tuple(t.clone() for t in cache)
+    for i, t in enumerate(dirty):
+        if fmt == "bf16":
+            t[:, :, pos + T:] = float("nan")
+            assert (t[:, :, pos + T:].view(torch.int16) == 0x7FC0).all()
+        else:
+            t[:, :, pos + T:] = 0xFF if i % 2 else 0x7F
+    clean_out = _call(fmt, q3, k3, v3, cache, table, pos, rep)
+    dirty_out = _call(fmt, q3, k3, v3, dirty, table, pos, rep)
+    assert torch.isfinite(dirty_out.float()).all()
+    assert torch.equal(clean_out, dirty_out)
+    for a, b in zip(cache, dirty):
+        assert torch.equal(a[:, :, :pos + T], b[:, :, :pos + T])
+
+
+# ---------------------------------------------------------------------------
+# 3. K dim map
+# ---------------------------------------------------------------------------
+
+@pytest.mark.parametrize("fmt", FORMATS)
+def test_probe_k_dims(fmt):
+    """rep 8, T 8: 64 query rows, tokens 0..3 in the first MFMA row block and
+    4..7 in the second.  Every query is 64 at dim d only; the target row's K
+    is 64 at d only, every other row (the new ones included) 64 everywhere
+    BUT d: log2-score ~522 against 0, every token returns the target's V.
+    128 pairs probe the 128 dims."""
+    nb, nh, rep, T, pos = 16, 8, 8, 8, 40
+    Smax = pos + T + 2
+    pair = torch.arange(nb * nh)
+    d = pair % D
+    rstar = (7 * pair + 3) % pos
+    onehot = torch.nn.functional.one_hot(d, D).float() * 64.0   # (pairs, D)
+    K = (64.0 - onehot).reshape(nb, nh, 1, D).repeat(1, 1, Smax, 1)
+    K[pair // nh, pair % nh, rstar] = onehot
+    V = _grid(nb, nh, Smax)
+    k3, v3 = _to3(K[:, :, pos:pos + T]), _to3(V[:, :, pos:pos + T])
+    K[:, :, pos:] = 0
+    V[:, :, pos:] = 0
+    cache = _make_cache(fmt, K, V)
+    q3 = onehot.reshape(nb, 1, nh, 1, D).expand(nb, T, nh, rep, D) \
+        .reshape(nb, T, nh * rep * D).bfloat16().cuda()
+    out = _call(fmt, q3, k3, v3, cache, _identity_table(Smax), pos, rep)
+    vd = _v_stored(fmt, cache)
+    want = vd[(pair // nh).cuda(), (pair % nh).cuda(), rstar.cuda()]
+    want = want.view(nb, 1, nh, 1, D).expand(nb, T, nh, rep, D)
+    got = out.view(nb, T, nh, rep, D)
+    bad = (got != want).any(-1).nonzero()
+    assert torch.equal(got, want), f"{fmt}: (b, t, kvh, g) {bad[:8].tolist()}"
+
+
+# ---------------------------------------------------------------------------
+# 4. random numerics, 5. appended rows
+# ---------------------------------------------------------------------------
+
+def _rope32(x, cos, sin, pos):   # x (..., D) at one position, fp32
+    c, s = cos[pos].float(), sin[pos].float()
+    x = x.float()
+    x1, x2 = x[..., :D // 2], x[..., D // 2:]
+    return torch.cat([x1 * c - x2 * s, x2 * c + x1 * s], dim=-1)
+
+
+def _ref64(q2, K64, V64, table, p, rep):
+    """fp64 attention of the fp32-roped q2 (nb, nh*rep*D) at position p over
+    rows [0, p] of K64, V64 -> (nb, nh*rep*D)."""
+    nb, nh = K64.shape[:2]
+    q = _rope32(q2.view(nb, nh * rep, D), *table, p).double()
+    kx = K64[:, :, :p + 1].repeat_interleave(rep, dim=1)
+    vx = V64[:, :, :p + 1].repeat_interleave(rep, dim=1)
+    att = torch.softmax((q.unsqueeze(2) @ kx.transpose(-1, -2)) * SCALE, -1)
+    return (att @ vx).squeeze(2).reshape(nb, nh * rep * D)
+
+
+def _chunk_error(fmt, q3, cache, out, table, pos, rep):
+    T = q3.shape[1]
+    K64, V64 = _kv64(fmt, cache)
+    return max((out[:, t].double()
+                - _ref64(q3[:, t], K64, V64, table, pos + t, rep))
+               .abs().max().item() for t in range(T))
+
+
+def _sequential(fmt, q3, k3, v3, cache, table, pos, rep):
+    """The single-token kernel T times on the same inputs: its max error
+    against fp64 over ITS cache as stored after each step."""
+    nh = cache[0].shape[1]
+    fn = ops.decode_attn_step if fmt == "bf16" else ops.decode_attn_mx_step
+    err = 0.0
+    for t in range(q3.shape[1]):
+        out = fn(q3[:, t], k3[:, t], v3[:, t], *cache, *table,
+                 _pos_t(pos + t), nh * rep, nh, SCALE)
+        K64, V64 = _kv64(fmt, cache)
+        err = max(err, (out.double() - _ref64(q3[:, t], K64, V64, table,
+                                              pos + t, rep)).abs().max().item())
+    return err
+
+
+def _bound(err_seq):
+    return min(ALLOWED_RATIO * err_seq, ATOL_CAP)
+
+
+def _check_appended(fmt, cache, before, seq_cache, k3, v3, table, pos, T):
+    nb, nh = cache[0].shape[:2]
+    for a, b in zip(cache, before):    # rows outside [pos, pos + T)
+        assert torch.equal(a[:, :, :pos], b[:, :, :pos])
+        assert torch.equal(a[:, :, pos + T:], b[:, :, pos + T:])
+    v_in = v3.view(nb, T, nh, D).transpose(1, 2)
+    k_in = k3.view(nb, T, nh, D).transpose(1, 2)
+    k_ref = torch.stack([_rope32(k_in[:, :, t], *table, pos + t)
+                         for t in range(T)], 2)              # fp32
+    if fmt == "bf16":
+        assert torch.equal(cache[1][:, :, pos:pos + T], v_in)
+        # K: within one bf16 ulp of the rows the single-token kernel stores
+        got = cache[0][:, :, pos:pos + T].view(torch.int16).int()
+        seq = seq_cache[0][:, :, pos:pos + T].view(torch.int16).int()
+        assert (got - seq).abs().max() <= 1
+        return
+    kp, ks, vp, vs = (t[:, :, pos:pos + T].cpu() for t in cache)
+    ep, es = _packed(v_in.cpu().float())
+    assert torch.equal(vp, ep) and torch.equal(vs, es)
+    # K, as test_decode_attn_mx_gpu.py checks the single-row append:
+    # (a) canonical encoding, but for a block whose scaled amax rounded down
+    #     to 224 (224 * 2^e re-quantizes as 448 * 2^(e-1): the same values)
+    kq, ke = unpack_mx(kp, ks, FMT)
+    kd = dequantize_mx(kq, ke, dtype=torch.float32)
+    rp, rs = _packed(kd)
+    same = rs == ks
+    amax224 = kq.reshape(nb, nh, T, D // 32, 32).abs().amax(-1) == 224
+    assert (same | amax224).all()
+    assert torch.equal(dequantize_mx(*unpack_mx(rp, rs, FMT),
+                                     dtype=torch.float32), kd)
+    same_e = same.repeat_interleave(32, dim=-1)
+    assert torch.equal(rp[same_e], kp[same_e])
+    # (b) one e4m3 ulp (normal) or one subnormal step from the fp32 row
+    step = torch.exp2(ke - 9).repeat_interleave(32, dim=-1)
+    assert ((kd - k_ref.cpu()).abs() <= k_ref.cpu().abs() / 8 + step).all()
+
+
+@pytest.mark.parametrize("T", TS)
+@pytest.mark.parametrize("rep", REPS)
+@pytest.mark.parametrize("fmt", FORMATS)
+def test_random_numerics(fmt, rep, T):
+    worst = (0.0, 0.0, 0.0)
+    for pos in POS:
+        Smax = pos + T + 3
+        table = _rope_table(Smax)
+        cache, q3, k3, v3 = _random_case(fmt, rep, T, pos, Smax,
+                                         11 + 1000 * rep + 10 * pos + T)
+        before = tuple(t.clone() for t in cache)
+        seq_cache = tuple(t.clone() for t in cache)
+        err_seq = _sequential(fmt, q3, k3, v3, seq_cache, table, pos, rep)
+        out = _call(fmt, q3, k3, v3, cache, table, pos, rep)
+        assert torch.isfinite(out.float()).all()
+        err = _chunk_error(fmt, q3, cache, out, table, pos, rep)
+        print(f"chunk_attn {fmt} rep {rep} T {T} pos {pos}: max err "
+              f"{err:.3e}, {T} single-token steps {err_seq:.3e}, ratio "
+              f"{err / err_seq:.3f}, bound {_bound(err_seq):.3e}")
+        worst = max(worst, (err / err_seq, err, err_seq))
+        assert err <= _bound(err_seq), (pos, err, err_seq)
+        _check_appended(fmt, cache, before, seq_cache, k3, v3, table, pos, T)
+    print(f"chunk_attn {fmt} rep {rep} T {T}: WORST ratio {worst[0]:.3f} "
+          f"(err {worst[1]:.3e} vs {worst[2]:.3e})")
+
+
+# ---------------------------------------------------------------------------
+# 6. end-of-cache guard
+# ---------------------------------------------------------------------------
+
+@pytest.mark.parametrize("fmt", FORMATS)
+def test_end_of_cache_guard(fmt):
+    """pos = Smax - 2 with T = 4: rows Smax, Smax + 1 do not exist.  The
+    caches are the [:B] view of an allocation of B + 1 batches whose last
+    batch is a canary, so a write past a (b, kvh) pair's rows would land in
+    rows 0.. of the next pair or in the canary, inside the allocation."""
+    rep, T, Smax = 4, 4, 40
+    pos = Smax - 2
+    table = _rope_table(Smax)
+    big, q3, k3, v3 = _random_case(fmt, rep, T, pos, Smax, 31, nb=B + 1)
+    q3, k3, v3 = q3[:B], k3[:B], v3[:B]
+    for t in big:
+        t[B] = 0x5A if t.dtype == torch.uint8 else 7.0
+    before = tuple(t.clone() for t in big)
+    cache = tuple(t[:B] for t in big)
+    assert all(t.is_contiguous() for t in cache)
+    out = _call(fmt, q3, k3, v3, cache, table, pos, rep)
+    torch.cuda.synchronize()
+    for a, b in zip(big, before):
+        assert torch.equal(a[B], b[B])                      # the canary
+        assert torch.equal(a[:B, :, :pos], b[:B, :, :pos])  # rows 0..pos-1
+        assert not torch.equal(a[:B, :, pos:], b[:B, :, pos:])
+    K64, V64 = _kv64(fmt, cache)
+    for t in (0, 1):
+        ref = _ref64(q3[:, t], K64, V64, table, pos + t, rep)
+        assert (out[:, t].double() - ref).abs().max() <= ATOL_CAP
+
+
+# ---------------------------------------------------------------------------
+# 7. determinism, 8. graph capture
+# ---------------------------------------------------------------------------
+
+@pytest.mark.parametrize("fmt", FORMATS)
+def test_deterministic(fmt):
+    rep, T, pos = 8, 5, 129
+    Smax = pos + T + 3
+    cache, q3, k3, v3 = _random_case(fmt, rep, T, pos, Smax, 21)
+    c2 = tuple(t.clone() for t in cache)
+    table = _rope_table(Smax)
+    o1 = _call(fmt, q3, k3, v3, cache, table, pos, rep)
+    o2 = _call(fmt, q3, k3, v3, c2, table, pos, rep)
+    assert torch.equal(o1, o2)
+    for a, b in zip(cache, c2):
+        assert torch.equal(a, b)
+
+
+@pytest.mark.parametrize("fmt", FORMATS)
+def test_graph_replay_matches_eager(fmt):
+    rep, T, pos0, steps = 4, 4, 27, 3
+    Smax = pos0 + steps * T + 2
+    table = _rope_table(Smax)
+    cache, _, _, _ = _random_case(fmt, rep, T, pos0, Smax, 22)
+    ins = [_random_case(fmt, rep, T, 0, 1, 23 + i)[1:] for i in range(steps)]
+    eager_cache = tuple(t.clone() for t in cache)
+    eager = [_call(fmt, *ins[i], eager_cache, table, pos0 + i * T, rep)
+             for i in range(steps)]
+
+    q_s, k_s, v_s = (t.clone() for t in ins[0])
+    pos_t = _pos_t(pos0)
+    warm = tuple(t.clone() for t in cache)   # warm-up touches a copy only
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        _call(fmt, q_s, k_s, v_s, warm, table, pos_t, rep)
+    torch.cuda.current_stream().wait_stream(side)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        out_s = _call(fmt, q_s, k_s, v_s, cache, table, pos_t, rep)
+    for i in range(steps):
+        for dst, src in zip((q_s, k_s, v_s), ins[i]):
+            dst.copy_(src)
+        graph.replay()
+        assert torch.equal(out_s, eager[i]), i
+        pos_t += T
+    for a, b in zip(cache, eager_cache):
+        assert torch.equal(a, b)
+
+
+def test_strided_qkv_views():
+    """q, k, v as slices of one fused-QKV GEMM output (row stride > width)
+    give the outputs of dense copies."""
+    rep, T, pos = 4, 3, 33
+    Smax = pos + T + 1
+    table = _rope_table(Smax)
+    cache, q3, k3, v3 = _random_case("bf16", rep, T, pos, Smax, 41)
+    c2 = tuple(t.clone() for t in cache)
+    wq, wk = HKV * rep * D, HKV * D
+    # k and v get equal widths so that they share their strides
+    fused = torch.zeros(B, T, wq + 2 * wk, dtype=torch.bfloat16, device="cuda")
+    fused[..., :wq], fused[..., wq:wq + wk], fused[..., wq + wk:] = q3, k3, v3
+    views = (fused[..., :wq], fused[..., wq:wq + wk], fused[..., wq + wk:])
+    assert not views[0].is_contiguous()
+    o1 = _call("bf16", q3, k3, v3, cache, table, pos, rep)
+    o2 = _call("bf16", *views, c2, table, pos, rep)
+    assert torch.equal(o1, o2)
+    for a, b in zip(cache, c2):
+        assert torch.equal(a, b)
+
+
+# ---------------------------------------------------------------------------
+# 9. guards
+# ---------------------------------------------------------------------------
+
+def test_guards():
+    rep, T, pos, Smax = 2, 3, 2, 8
+    cos, sin = _rope_table(Smax)
+    z = lambda *s, dt=torch.bfloat16: torch.zeros(  # noqa: E731
+        *s, dtype=dt, device="cuda")
+    mx = (z(B, HKV, Smax, D, dt=torch.uint8),
+          z(B, HKV, Smax, D // 32, dt=torch.uint8),
+          z(B, HKV, Smax, D, dt=torch.uint8),
+          z(B, HKV, Smax, D // 32, dt=torch.uint8))
+    bf = (z(B, HKV, Smax, D), z(B, HKV, Smax, D))
+    q = lambda t, r=rep: torch.ones(B, t, HKV * r * D,  # noqa: E731
+                                    dtype=torch.bfloat16, device="cuda")
+    kv = lambda t: torch.ones(B, t, HKV * D, dtype=torch.bfloat16,  # noqa
+                              device="cuda")
+    tail = (_pos_t(pos), HKV * rep, HKV, SCALE)
+    both = ((ops.chunk_attn_step, bf), (ops.chunk_attn_mx_step, mx))
+    for fn, cache in both:
+        for t in (1, 9):                                  # T outside 2..8
+            with pytest.raises(ValueError):
+                fn(q(t), kv(t), kv(t), *cache, cos, sin, *tail)
+        with pytest.raises(ValueError):                   # GQA rep 3
+            fn(q(T, 3), kv(T), kv(T), *cache, cos, sin, _pos_t(pos), HKV * 3,
+               HKV, SCALE)
+        with pytest.raises(ValueError):                   # fp16 q
+            fn(q(T).half(), kv(T), kv(T), *cache, cos, sin, *tail)
+        with pytest.raises(ValueError):                   # short RoPE table
+            fn(q(T), kv(T), kv(T), *cache, cos[:Smax - 1], sin[:Smax - 1],
+               *tail)
+        with pytest.raises(ValueError):                   # two positions
+            fn(q(T), kv(T), kv(T), *cache, cos, sin,
+               torch.tensor([pos, pos], device="cuda"), *tail[1:])
+        with pytest.raises(ValueError):                   # Smax < T
+            fn(q(T), kv(T), kv(T), *(c[:, :, :T - 1].contiguous()
+                                     for c in cache), cos, sin, *tail)
+        with pytest.raises(ValueError):                   # k, v strides differ
+            wide = torch.ones(B, T, 2 * HKV * D, dtype=torch.bfloat16,
+                              device="cuda")
+            fn(q(T), wide[..., :HKV * D], kv(T), *cache, cos, sin, *tail)
+    with pytest.raises(ValueError):          # uint8 caches, bf16 entry
+        ops.chunk_attn_step(q(T), kv(T), kv(T), mx[0], mx[2], cos, sin, *tail)
+    with pytest.raises(ValueError):          # bf16 caches, MX entry
+        ops.chunk_attn_mx_step(q(T), kv(T), kv(T), bf[0], mx[1], bf[1], mx[3],
+                               cos, sin, *tail)
+    torch.cuda.synchronize()
+    for t in mx + bf:                        # nothing was launched
+        assert not t.any()
+
+
+# ---------------------------------------------------------------------------
+# 10. model level
+# ---------------------------------------------------------------------------
+
+def _llama(seed=0):
+    import torch.distributed as dist
+    from neuronx_distributed_amd.models import LlamaForCausalLM, get_config
+    from neuronx_distributed_amd.parallel import parallel_state as ps
+
+    if not dist.is_initialized():
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        os.environ.setdefault("MASTER_PORT", "29557")
+        dist.init_process_group("nccl", rank=0, world_size=1)
+    if not ps.model_parallel_is_initialized():
+        ps.initialize_model_parallel(tensor_model_parallel_size=1)
+    cfg = get_config("test-d128")   # 2 layers, hidden 512, Hq 4, Hkv 2, D 128
+    prev = torch.get_default_dtype()
+    torch.set_default_dtype(torch.bfloat16)
+    torch.manual_seed(seed)
+    with torch.device("cuda"):
+        model = LlamaForCausalLM(cfg)
+    torch.set_default_dtype(prev)
+    return cfg, model.eval()
+
+
+def _count(monkeypatch):
+    calls = {"bf16": 0, "mx": 0}
+    real = {"bf16": ops.chunk_attn_step, "mx": ops.chunk_attn_mx_step}
+
+    def wrap(key):
+        def f(*a, **kw):
+            calls[key] += 1
+            return real[key](*a, **kw)
+        return f
+
+    monkeypatch.setattr(ops, "chunk_attn_step", wrap("bf16"))
+    monkeypatch.setattr(ops, "chunk_attn_mx_step", wrap("mx"))
+    return calls
+
+
+LOGIT_ATOL = 5e-2   # the closeness test_gpu_e2e.py asks of two bf16 paths
+
+
+@pytest.mark.parametrize("kv_format", [None, "mxfp8"])
+def test_model_chunk_matches_reference(kv_format, monkeypatch):
+    """model(chunk, pos_offset=tensor), the fused kernels, against the same
+    weights on another path: for the bf16 cache the int-position forward
+    (rectangular attention over the prefix), for mxfp8 the eager chain of
+    LlamaAttention._chunk_step itself (kernels made unavailable).
+
+    Cache rows: layer 0 of both runs sees identical hidden states, so its V
+    rows are bit-equal and its K rows within one bf16 ulp (MX: the same
+    bytes for V).  A later layer's K/V projections see hidden states that
+    already differ by the two attention paths' rounding, so its rows can
+    only be close: the logit tolerance."""
+    from neuronx_distributed_amd.inference.kv_cache import build_kv_caches
+
+    cfg, model = _llama()
+    calls = _count(monkeypatch)
+    Bm, P, T = 2, 11, 4
+    torch.manual_seed(1)
+    x = torch.randint(0, cfg.vocab_size, (Bm, P + T), device="cuda")
+    mk = lambda: build_kv_caches(  # noqa: E731
+        cfg.num_hidden_layers, Bm, cfg.num_key_value_heads, 32, cfg.head_dim,
+        device="cuda", kv_format=kv_format)
+    c1, c2 = mk(), mk()
+    key = "mx" if kv_format else "bf16"
+    with torch.no_grad():
+        for c in (c1, c2):
+            model(x[:, :P], kv_caches=c, pos_offset=0)
+        got = model(x[:, P:], kv_caches=c1, pos_offset=_pos_t(P))
+        assert calls[key] == cfg.num_hidden_layers and sum(calls.values()) \
+            == cfg.num_hidden_layers
+        if kv_format is None:
+            want = model(x[:, P:], kv_caches=c2, pos_offset=P)
+        else:
+            monkeypatch.setattr(ops, "chunk_attn_mx_available", lambda: False)
+            want = model(x[:, P:], kv_caches=c2, pos_offset=_pos_t(P))
+        assert sum(calls.values()) == cfg.num_hidden_layers
+    assert got.shape == want.shape == (Bm, T, cfg.vocab_size)
+    err = (got.float() - want.float()).abs().max().item()
+    print(f"model chunk step {kv_format}: max logit diff {err:.3e} "
+          f"(logits up to {want.float().abs().max().item():.2f})")
+    assert err <= LOGIT_ATOL
+    for a, b in zip(c1, c2):
+        for t in ("k", "v"):     # the prefill rows, and nothing past the chunk
+            assert torch.equal(getattr(a, t)[:, :, :P],
+                               getattr(b, t)[:, :, :P])
+            assert not getattr(a, t)[:, :, P + T:].any()
+        if kv_format is None:
+            if a is c1[0]:
+                assert torch.equal(a.v, b.v)
+                dk = a.k.view(torch.int16).int() - b.k.view(torch.int16).int()
+                assert dk.abs().max() <= 1
+            else:
+                for t in ("k", "v"):
+                    d = (getattr(a, t).float() - getattr(b, t).float()).abs()
+                    assert d.max() <= LOGIT_ATOL
+        elif a is c1[0]:
+            assert torch.equal(a.v, b.v)
+            assert torch.equal(a.v_scale, b.v_scale)
+
+
+@pytest.mark.parametrize("kv_format", [None, "mxfp8"])
+def test_speculative_generate_fused_verify(kv_format, monkeypatch):
+    from neuronx_distributed_amd.inference.speculation import (
+        speculative_generate)
+
+    cfg, target = _llama(0)
+    _, draft = _llama(5)
+    calls = _count(monkeypatch)
+    torch.manual_seed(2)
+    x = torch.randint(0, cfg.vocab_size, (2, 9), device="cuda")
+    out, rate = speculative_generate(target, draft, x, max_new_tokens=8,
+                                     spec_len=3, kv_format=kv_format,
+                                     fused_verify=True)
+    assert out.shape == (2, 17) and torch.equal(out[:, :9], x)
+    assert 0.0 <= rate <= 1.0
+    key = "mx" if kv_format else "bf16"
+    assert calls[key] > 0 and calls["bf16" if kv_format else "mx"] == 0
