@@ -7,7 +7,7 @@ reference's traced/compiled token-generation model (reference
 trace/model_builder + nxd_model bucket executor).
 
 The step is made capturable by driving every position-dependent piece of
-the model from DEVICE tensors (see ``LlamaAttention._decode_step`` and
+the model from DEVICE tensors (see ``LlamaAttention._cached_step`` and
 ``KVCache.update`` tensor-pos paths): between replays only the contents
 of ``step_in`` (next token) and ``pos_t`` change.
 """

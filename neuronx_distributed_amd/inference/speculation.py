@@ -25,7 +25,7 @@ def _greedy(logits: torch.Tensor) -> torch.Tensor:
 def _chunk_pos(pos: int, n_tokens: int, fused: bool, device):
     """The position argument of a multi-token forward at ``pos``: a device
     int64 tensor, which routes attention to the fused chunk step
-    (LlamaAttention._chunk_step), when ``fused`` and the forward is one that
+    (LlamaAttention._cached_step), when ``fused`` and the forward is one that
     step takes (2..8 tokens against a cache that holds rows); else the int."""
     if fused and pos > 0 and 2 <= n_tokens <= 8:
         return torch.tensor([pos], dtype=torch.long, device=device)

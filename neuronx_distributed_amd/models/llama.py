@@ -208,16 +208,13 @@ class LlamaAttention(nn.Module):
             # hipGraph-capturable decode: device-tensor position, S == 1
             # (or a chunk of 2..8 tokens: speculative verification),
             # full-cache masked attention (no dynamic shapes)
-            if S == 1:
-                return self._decode_step(q, k, v, cos, sin, pos_offset,
-                                         kv_cache, sp)
-            if not 2 <= S <= 8:
+            if not 1 <= S <= 8:
                 raise ValueError(
                     f"a device-tensor position takes 1..8 tokens per "
                     f"forward, got {S}; use an int position for a longer "
                     f"chunk")
-            return self._chunk_step(q, k, v, cos, sin, pos_offset, kv_cache,
-                                    sp)
+            return self._cached_step(q, k, v, cos, sin, pos_offset, kv_cache,
+                                     sp)
         q, k = ops.apply_rotary_pos_emb(q, k, cos, sin, pos_offset)
 
         # (B,S,h,D) -> (B,h,S,D)
@@ -242,139 +239,69 @@ class LlamaAttention(nn.Module):
             out = out.transpose(0, 1)
         return self.o_proj(out)
 
-    def _decode_step(self, q, k, v, cos, sin, pos_t, kv_cache, sp):
-        """One-token decode with everything derived from the device tensor
-        ``pos_t`` (shape (1,)) so the whole step can be captured in a
-        hipGraph and replayed with only memory updates between steps.
+    def _cached_step(self, q, k, v, cos, sin, pos_t, kv_cache, sp):
+        """S = 1..8 new tokens at the device position ``pos_t`` (shape (1,)):
+        token t is roped at pos + t, written to cache row pos + t and attends
+        rows [0, pos + t].  Everything derives from the device tensor, so the
+        whole step can be captured in a hipGraph and replayed with only
+        memory updates between steps.
 
         On GPU with D=128 the whole chain (RoPE + cache append +
-        flash-decode + GQA) is ONE fused HIP kernel, chosen by the cache's
-        type: ops.decode_attn_step for a plain bf16 KVCache,
-        ops.decode_attn_mx_step for an MXKVCache.  Any other cache, and the
-        CPU and odd shapes, take the torch chain below (the reference)."""
-        from ..inference.kv_cache import KVCache, MXKVCache
-
-        B = q.shape[0]
-        rep = self.num_heads_local // self.num_kv_local
-        fusable = (q.is_cuda and self.head_dim == 128 and rep in (1, 2, 4, 8)
-                   and q.dtype == torch.bfloat16
-                   and self.sliding_window is None)
-        fused_bf16 = (fusable and type(kv_cache) is KVCache
-                      and kv_cache.k.is_cuda
-                      and kv_cache.k.dtype == torch.bfloat16
-                      and ops.decode_attn_available())
-        fused_mx = (fusable and type(kv_cache) is MXKVCache
-                    and kv_cache.k.is_cuda
-                    and ops.decode_attn_mx_available())
-        if fused_bf16 or fused_mx:
-            def _flat(t):
-                # (B,1,h,D) -> (B, h*D) as a VIEW even for fused-QKV slices
-                # (batch stride may exceed h*D; decode_attn takes strides)
-                t = t.squeeze(1)
-                f = t.reshape(B, -1)
-                return f if f.stride(1) == 1 else t.contiguous().view(B, -1)
-
-            tail = (cos, sin, pos_t.reshape(1), self.num_heads_local,
-                    self.num_kv_local, 1.0 / math.sqrt(self.head_dim))
-            if fused_mx:
-                out = ops.decode_attn_mx_step(
-                    _flat(q), _flat(k), _flat(v), kv_cache.k,
-                    kv_cache.k_scale, kv_cache.v, kv_cache.v_scale, *tail)
-            else:
-                out = ops.decode_attn_step(
-                    _flat(q), _flat(k), _flat(v), kv_cache.k, kv_cache.v,
-                    *tail)
-            out = out.unsqueeze(1)  # (B, 1, H*D)
-            if sp:
-                out = out.transpose(0, 1)
-            return self.o_proj(out)
-        half = self.head_dim // 2
-        c = cos.index_select(0, pos_t).view(1, 1, 1, half)  # (1,1,1,D/2)
-        s = sin.index_select(0, pos_t).view(1, 1, 1, half)
-
-        def rope1(x):
-            x0 = x[..., :half].float()
-            x1 = x[..., half:].float()
-            return torch.cat([x0 * c - x1 * s, x1 * c + x0 * s],
-                             dim=-1).to(x.dtype)
-
-        q = rope1(q).transpose(1, 2)  # (B,h,1,D)
-        k = rope1(k).transpose(1, 2)
-        v = v.transpose(1, 2)
-        K, V = kv_cache.update(k, v, pos_t)  # FULL (B,Hkv,Smax,D) buffers
-        Smax = K.shape[2]
-        rep = self.num_heads_local // self.num_kv_local
-        scale = 1.0 / math.sqrt(self.head_dim)
-        # bf16 batched GEMV against the cache (fp32 accumulation inside the
-        # GEMM; casting K/V to fp32 would re-materialize the whole cache
-        # every step) -> (B,Hkv,rep,Smax)
-        qg = q.view(B, self.num_kv_local, rep, self.head_dim)
-        scores = (qg @ K.transpose(-1, -2)).float() * scale
-        if hasattr(kv_cache, "position_index"):
-            # rolling window cache: slots carry their GLOBAL position
-            # (-1 = unwritten -> masked by idx > pos_t never holding...
-            # masked via idx < 0 below)
-            idx = kv_cache.position_index()
-            invalid = (idx > pos_t) | (idx < 0)
-        else:
-            idx = torch.arange(Smax, device=q.device)
-            invalid = idx > pos_t
-        if self.sliding_window is not None:
-            invalid = invalid | (idx <= pos_t - self.sliding_window)
-        scores = scores.masked_fill(invalid, float("-inf"))
-        probs = torch.softmax(scores, dim=-1)
-        out = probs.to(q.dtype) @ V  # (B,Hkv,rep,D)
-        out = out.reshape(B, 1, self.num_heads_local * self.head_dim)
-        if sp:
-            out = out.transpose(0, 1)
-        return self.o_proj(out)
-
-    def _chunk_step(self, q, k, v, cos, sin, pos_t, kv_cache, sp):
-        """S = 2..8 new tokens at the device position ``pos_t``: token t is
-        roped at pos + t, written to cache row pos + t and attends rows
-        [0, pos + t].  Like :meth:`_decode_step` nothing depends on the host
-        knowing the position.
-
-        On GPU with D=128 this is ops.chunk_attn_step (plain bf16 KVCache)
-        or ops.chunk_attn_mx_step (MXKVCache); any other cache, the CPU and
-        odd shapes take the torch chain below (the reference)."""
+        flash-decode + GQA) is fused HIP, chosen by S and the cache's type:
+        ops.decode_attn_step / ops.chunk_attn_step for a plain bf16 KVCache,
+        ops.decode_attn_mx_step / ops.chunk_attn_mx_step for an MXKVCache.
+        Any other cache, and the CPU and odd shapes, take the torch chain
+        below (the reference)."""
         from ..inference.kv_cache import KVCache, MXKVCache
 
         B, S = q.shape[0], q.shape[1]
         rep = self.num_heads_local // self.num_kv_local
         scale = 1.0 / math.sqrt(self.head_dim)
+        mx = type(kv_cache) is MXKVCache
         fusable = (q.is_cuda and self.head_dim == 128 and rep in (1, 2, 4, 8)
                    and q.dtype == torch.bfloat16
-                   and self.sliding_window is None)
-        fused_bf16 = (fusable and type(kv_cache) is KVCache
-                      and kv_cache.k.is_cuda
-                      and kv_cache.k.dtype == torch.bfloat16
-                      and ops.chunk_attn_available())
-        fused_mx = (fusable and type(kv_cache) is MXKVCache
-                    and kv_cache.k.is_cuda
-                    and ops.chunk_attn_mx_available())
-        if fused_bf16 or fused_mx:
-            def _flat(t):
-                # (B,S,h,D) -> (B,S,h*D) as a VIEW of a fused-QKV slice where
-                # its strides allow (the kernels take row strides)
-                f = t.reshape(B, S, -1)
-                ok = (f.stride(2) == 1 and f.stride(1) >= f.shape[2]
-                      and f.stride(0) % 8 == 0 and f.stride(1) % 8 == 0
-                      and f.data_ptr() % 16 == 0)
-                return f if ok else f.contiguous()
-
-            q3, k3, v3 = _flat(q), _flat(k), _flat(v)
-            if k3.stride() != v3.stride():
-                k3, v3 = k3.contiguous(), v3.contiguous()
-            tail = (cos, sin, pos_t.reshape(1), self.num_heads_local,
-                    self.num_kv_local, scale)
-            if fused_mx:
-                out = ops.chunk_attn_mx_step(
-                    q3, k3, v3, kv_cache.k, kv_cache.k_scale, kv_cache.v,
-                    kv_cache.v_scale, *tail)
+                   and self.sliding_window is None
+                   and (mx or (type(kv_cache) is KVCache
+                               and kv_cache.k.dtype == torch.bfloat16))
+                   and kv_cache.k.is_cuda)
+        if fusable:  # ops.* looked up per call: the tests patch them
+            if S == 1:
+                fusable = (ops.decode_attn_mx_available() if mx
+                           else ops.decode_attn_available())
+                step = ops.decode_attn_mx_step if mx else ops.decode_attn_step
             else:
-                out = ops.chunk_attn_step(q3, k3, v3, kv_cache.k, kv_cache.v,
-                                          *tail)
+                fusable = (ops.chunk_attn_mx_available() if mx
+                           else ops.chunk_attn_available())
+                step = ops.chunk_attn_mx_step if mx else ops.chunk_attn_step
+        if fusable:
+            if S == 1:
+                def _flat(t):
+                    # (B,1,h,D) -> (B, h*D) as a VIEW even for fused-QKV
+                    # slices (batch stride may exceed h*D; decode_attn takes
+                    # strides)
+                    t = t.squeeze(1)
+                    f = t.reshape(B, -1)
+                    return f if f.stride(1) == 1 \
+                        else t.contiguous().view(B, -1)
+            else:
+                def _flat(t):
+                    # (B,S,h,D) -> (B,S,h*D) as a VIEW of a fused-QKV slice
+                    # where its strides allow (the kernels take row strides)
+                    f = t.reshape(B, S, -1)
+                    ok = (f.stride(2) == 1 and f.stride(1) >= f.shape[2]
+                          and f.stride(0) % 8 == 0 and f.stride(1) % 8 == 0
+                          and f.data_ptr() % 16 == 0)
+                    return f if ok else f.contiguous()
+
+            qf, kf, vf = _flat(q), _flat(k), _flat(v)
+            if S > 1 and kf.stride() != vf.stride():
+                kf, vf = kf.contiguous(), vf.contiguous()
+            bufs = (kv_cache.k, kv_cache.k_scale, kv_cache.v,
+                    kv_cache.v_scale) if mx else (kv_cache.k, kv_cache.v)
+            out = step(qf, kf, vf, *bufs, cos, sin, pos_t.reshape(1),
+                       self.num_heads_local, self.num_kv_local, scale)
+            if S == 1:
+                out = out.unsqueeze(1)  # (B, 1, H*D)
             if sp:
                 out = out.transpose(0, 1)
             return self.o_proj(out)
@@ -396,15 +323,22 @@ class LlamaAttention(nn.Module):
         if K.dtype != q.dtype:  # a cache kept in another dtype than the model
             K, V = K.to(q.dtype), V.to(q.dtype)
         Smax = K.shape[2]
-        # (B,Hkv,rep*S,D) against the cache -> (B,Hkv,rep,S,Smax)
+        # bf16 batched GEMM against the cache (fp32 accumulation inside the
+        # GEMM; casting K/V to fp32 would re-materialize the whole cache
+        # every step): (B,Hkv,rep*S,D) -> (B,Hkv,rep,S,Smax)
         qg = q.reshape(B, self.num_kv_local, rep * S, self.head_dim)
         scores = (qg @ K.transpose(-1, -2)).float() * scale
         scores = scores.view(B, self.num_kv_local, rep, S, Smax)
-        idx = torch.arange(Smax, device=q.device)
-        invalid = idx.view(1, Smax) > tpos.view(S, 1)  # (S, Smax)
+        if hasattr(kv_cache, "position_index"):
+            # rolling window cache (S == 1, its update refuses more): slots
+            # carry their GLOBAL position, -1 = unwritten
+            idx = kv_cache.position_index().view(1, Smax)
+            invalid = (idx > tpos.view(S, 1)) | (idx < 0)  # (S, Smax)
+        else:
+            idx = torch.arange(Smax, device=q.device).view(1, Smax)
+            invalid = idx > tpos.view(S, 1)
         if self.sliding_window is not None:
-            invalid = invalid | (idx.view(1, Smax)
-                                 <= tpos.view(S, 1) - self.sliding_window)
+            invalid = invalid | (idx <= tpos.view(S, 1) - self.sliding_window)
         scores = scores.masked_fill(invalid, float("-inf"))
         probs = torch.softmax(scores, dim=-1).to(q.dtype)
         out = probs.view(B, self.num_kv_local, rep * S, Smax) @ V

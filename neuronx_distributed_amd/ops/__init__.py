@@ -922,32 +922,53 @@ def decode_attn_available() -> bool:
 
 _DA_D = 128     # head dim of the fused decode kernels
 _DA_SPLIT = 4   # DA_SPLIT of csrc/decode_attn_common.h
+_CA_TMIN, _CA_TMAX = 2, 8   # CA_TMIN / CA_TMAX of csrc/chunk_attn.hip
 
 
-def _decode_attn_check(who, q2, k2, v2, cos, sin, pos_t, B, Hq, Hkv, Smax,
+def _decode_attn_check(who, chunk, q, k, v, cos, sin, pos_t, B, Hq, Hkv, Smax,
                        dev):
-    """Everything but the cache, for both fused decode kernels.  Returns the
-    (q, kv) row strides to launch with: the dense widths when B = 1."""
+    """Everything but the cache, for the four fused decode kernels: 2-D
+    q2/k2/v2 (one token) or, with ``chunk``, 3-D q3/k3/v3 (T = 2..8 tokens).
+    Returns T and the strides to launch with.  One token: the (q, kv) row
+    strides, the dense widths when B = 1; 2-byte alignment.  A chunk: the
+    element strides (q batch, q token, kv batch, kv token), multiples of 8,
+    and 16-byte pointers."""
     D = _DA_D
     if Hkv < 1 or Hq % Hkv or Hq // Hkv not in (1, 2, 4, 8):
         raise ValueError(f"{who}: Hq={Hq}, Hkv={Hkv} outside the kernel "
                          f"contract (GQA rep 1/2/4/8)")
-    for name, t, width in (("q2", q2, Hq * D), ("k2", k2, Hkv * D),
-                           ("v2", v2, Hkv * D)):
-        if t.dtype != torch.bfloat16 or t.device != dev or t.dim() != 2 \
-                or tuple(t.shape) != (B, width) or t.stride(1) != 1 \
-                or (B > 1 and t.stride(0) < width) or t.data_ptr() % 2:
-            raise ValueError(f"{who}: {name} must be a bf16 ({B}, {width}) "
-                             f"tensor on {dev} with a dense last dim, got "
+    if chunk and (q.dim() != 3 or not _CA_TMIN <= q.shape[1] <= _CA_TMAX):
+        raise ValueError(f"{who}: q3 {tuple(q.shape)} must be (B, T, Hq*128) "
+                         f"with {_CA_TMIN} <= T <= {_CA_TMAX}")
+    T = q.shape[1] if chunk else 1
+    if Smax < T:
+        raise ValueError(f"{who}: a cache of {Smax} rows cannot take {T} "
+                         f"tokens")
+    n, align = (3, 16) if chunk else (2, 2)
+    for name, t, width in ((f"q{n}", q, Hq * D), (f"k{n}", k, Hkv * D),
+                           (f"v{n}", v, Hkv * D)):
+        shape = (B, T, width) if chunk else (B, width)
+        ok = t.dtype == torch.bfloat16 and t.device == dev \
+            and tuple(t.shape) == shape and t.stride(-1) == 1 \
+            and t.data_ptr() % align == 0
+        if ok and chunk:
+            ok = t.stride(1) >= width and not (t.stride(0) % 8
+                                               or t.stride(1) % 8)
+        elif ok:
+            ok = B == 1 or t.stride(0) >= width
+        if not ok:
+            raise ValueError(f"{who}: {name} must be a {align}-byte aligned "
+                             f"bf16 {shape} tensor on {dev} with a dense "
+                             f"last dim and row strides that hold a row, got "
                              f"{t.dtype} {tuple(t.shape)} strides "
                              f"{t.stride()} on {t.device}")
-    if B > 1 and k2.stride(0) != v2.stride(0):
-        raise ValueError(f"{who}: k2 and v2 must share a row stride, got "
-                         f"{k2.stride(0)} and {v2.stride(0)}")
+    if k.stride() != v.stride() and (chunk or B > 1):
+        raise ValueError(f"{who}: k{n} and v{n} must share their strides, "
+                         f"got {k.stride()} and {v.stride()}")
     for name, t in (("cos", cos), ("sin", sin)):
         _mx_check_dense(f"{who}: {name}", t, torch.float32)
         if t.device != dev or t.dim() != 2 or t.shape[1] != D // 2 \
-                or t.shape[0] < Smax:
+                or t.shape[0] < Smax or (chunk and t.data_ptr() % 16):
             raise ValueError(f"{who}: {name} {tuple(t.shape)} on {t.device} "
                              f"must be (>= {Smax}, {D // 2}) on {dev}: the "
                              f"RoPE table covers the cache")
@@ -956,21 +977,61 @@ def _decode_attn_check(who, q2, k2, v2, cos, sin, pos_t, B, Hq, Hkv, Smax,
         raise ValueError(f"{who}: pos_t must be one int64 on {dev}, got "
                          f"{pos_t.dtype} {tuple(pos_t.shape)} on "
                          f"{pos_t.device}")
+    if chunk:
+        return T, tuple(ctypes.c_long(int(st)) for st in
+                        (q.stride(0), q.stride(1), k.stride(0), k.stride(1)))
     if B > 1:
-        return int(q2.stride(0)), int(k2.stride(0))
-    return Hq * D, Hkv * D
+        return T, (int(q.stride(0)), int(k.stride(0)))
+    return T, (Hq * D, Hkv * D)
 
 
-def _decode_attn_workspace(B, Hq, Hkv, dev):
-    """(part_o, part_ml, out); static shapes from the caching allocator, so
-    the pair of launches is hipGraph-capturable."""
-    rep = Hq // Hkv
-    part_o = torch.empty(B * Hkv * _DA_SPLIT, rep, _DA_D,
-                         dtype=torch.float32, device=dev)
-    part_ml = torch.empty(B * Hkv * _DA_SPLIT, rep, 2, dtype=torch.float32,
+def _decode_attn_check_cache(who, kcache, vcache, Hkv):
+    """The two buffers of a bf16 KVCache: contiguous (B, Hkv, Smax, 128) on
+    one GPU.  Returns (B, Smax)."""
+    for name, t in (("kcache", kcache), ("vcache", vcache)):
+        # an MXKVCache's uint8 buffers are half as large: the kernel would
+        # run past them
+        if t.dtype != torch.bfloat16 or t.dim() != 4 \
+                or t.shape[-1] != _DA_D or not t.is_cuda \
+                or not t.is_contiguous():
+            raise ValueError(f"{who}: {name} must be a contiguous bf16 "
+                             f"(B, Hkv, Smax, 128) GPU cache, got {t.dtype} "
+                             f"{tuple(t.shape)} on {t.device}")
+    if vcache.shape != kcache.shape or vcache.device != kcache.device \
+            or kcache.shape[1] != Hkv or min(kcache.shape) < 1:
+        raise ValueError(f"{who}: kcache {tuple(kcache.shape)} and vcache "
+                         f"{tuple(vcache.shape)} must be one non-empty shape "
+                         f"on one GPU with Hkv={Hkv} heads")
+    return kcache.shape[0], kcache.shape[2]
+
+
+def _decode_attn_workspace(B, T, Hq, Hkv, dev, chunk):
+    """(part_o, part_ml, out), out (B, T, Hq*128) for a chunk and (B, Hq*128)
+    for one token; static shapes from the caching allocator, so the launches
+    are hipGraph-capturable."""
+    R = Hq // Hkv * T
+    part_o = torch.empty(B * Hkv * _DA_SPLIT, R, _DA_D, dtype=torch.float32,
+                         device=dev)
+    part_ml = torch.empty(B * Hkv * _DA_SPLIT, R, 2, dtype=torch.float32,
                           device=dev)
-    out = torch.empty(B, Hq * _DA_D, dtype=torch.bfloat16, device=dev)
+    out = torch.empty((B, T, Hq * _DA_D) if chunk else (B, Hq * _DA_D),
+                      dtype=torch.bfloat16, device=dev)
     return part_o, part_ml, out
+
+
+def _decode_attn_launch(fn, chunk, tensors, B, T, Hq, Hkv, Smax, scale,
+                        strides):
+    """The C entry ``fn`` over q, k, v, the cache buffers, cos, sin and pos_t
+    (``tensors``) and a fresh workspace; a non-zero return, which launched
+    nothing, becomes ValueError."""
+    ws = _decode_attn_workspace(B, T, Hq, Hkv, tensors[-1].device, chunk)
+    rc = fn(*map(_ptr, tensors + ws), B, *((T,) if chunk else ()), Hq, Hkv,
+            Smax, ctypes.c_float(scale), *strides, _stream())
+    if rc != 0:
+        raise ValueError(f"{fn.__name__} rejected B={B}, T={T}, Hq={Hq}, "
+                         f"Hkv={Hkv}, Smax={Smax}, strides "
+                         f"{[getattr(st, 'value', st) for st in strides]}")
+    return ws[2]
 
 
 def decode_attn_step(q2: torch.Tensor, k2: torch.Tensor, v2: torch.Tensor,
@@ -988,33 +1049,14 @@ def decode_attn_step(q2: torch.Tensor, k2: torch.Tensor, v2: torch.Tensor,
     shape raises ValueError and launches nothing."""
     lib = _require_lib()
     who = "decode_attn_step"
-    for name, t in (("kcache", kcache), ("vcache", vcache)):
-        # an MXKVCache's uint8 buffers are half as large: the kernel would
-        # run past them
-        if t.dtype != torch.bfloat16 or t.dim() != 4 \
-                or t.shape[-1] != _DA_D or not t.is_cuda \
-                or not t.is_contiguous():
-            raise ValueError(f"{who}: {name} must be a contiguous bf16 "
-                             f"(B, Hkv, Smax, 128) GPU cache, got {t.dtype} "
-                             f"{tuple(t.shape)} on {t.device}")
-    if vcache.shape != kcache.shape or vcache.device != kcache.device \
-            or kcache.shape[1] != Hkv or min(kcache.shape) < 1:
-        raise ValueError(f"{who}: kcache {tuple(kcache.shape)} and vcache "
-                         f"{tuple(vcache.shape)} must be one non-empty shape "
-                         f"on one GPU with Hkv={Hkv} heads")
-    B, _, Smax, _ = kcache.shape
-    dev = kcache.device
-    qs, kvs = _decode_attn_check(who, q2, k2, v2, cos, sin, pos_t, B, Hq, Hkv,
-                                 Smax, dev)
-    part_o, part_ml, out = _decode_attn_workspace(B, Hq, Hkv, dev)
-    rc = lib.decode_attn(_ptr(q2), _ptr(k2), _ptr(v2), _ptr(kcache),
-                         _ptr(vcache), _ptr(cos), _ptr(sin), _ptr(pos_t),
-                         _ptr(part_o), _ptr(part_ml), _ptr(out), B, Hq, Hkv,
-                         Smax, ctypes.c_float(scale), qs, kvs, _stream())
-    if rc != 0:
-        raise ValueError(f"decode_attn rejected B={B}, Hq={Hq}, Hkv={Hkv}, "
-                         f"Smax={Smax}")
-    return out
+    if not decode_attn_available():
+        raise RuntimeError("nxd_ops library has no decode_attn — rebuild")
+    B, Smax = _decode_attn_check_cache(who, kcache, vcache, Hkv)
+    T, st = _decode_attn_check(who, False, q2, k2, v2, cos, sin, pos_t, B, Hq,
+                               Hkv, Smax, kcache.device)
+    return _decode_attn_launch(
+        lib.decode_attn, False, (q2, k2, v2, kcache, vcache, cos, sin, pos_t),
+        B, T, Hq, Hkv, Smax, scale, st)
 
 
 # ---------------------------------------------------------------------------
@@ -1354,18 +1396,12 @@ def decode_attn_mx_step(q2: torch.Tensor, k2: torch.Tensor, v2: torch.Tensor,
     if D != _DA_D or Hkv_c != Hkv:
         raise ValueError(f"{who}: cache {tuple(k_payload.shape)} with "
                          f"Hkv={Hkv} outside the kernel contract (D = 128)")
-    qs, kvs = _decode_attn_check(who, q2, k2, v2, cos, sin, pos_t, B, Hq, Hkv,
-                                 Smax, dev)
-    part_o, part_ml, out = _decode_attn_workspace(B, Hq, Hkv, dev)
-    rc = lib.decode_attn_mx(_ptr(q2), _ptr(k2), _ptr(v2), _ptr(k_payload),
-                            _ptr(k_scale), _ptr(v_payload), _ptr(v_scale),
-                            _ptr(cos), _ptr(sin), _ptr(pos_t), _ptr(part_o),
-                            _ptr(part_ml), _ptr(out), B, Hq, Hkv, Smax,
-                            ctypes.c_float(scale), qs, kvs, _stream())
-    if rc != 0:
-        raise ValueError(f"decode_attn_mx rejected B={B}, Hq={Hq}, "
-                         f"Hkv={Hkv}, Smax={Smax}")
-    return out
+    T, st = _decode_attn_check(who, False, q2, k2, v2, cos, sin, pos_t, B, Hq,
+                               Hkv, Smax, dev)
+    return _decode_attn_launch(
+        lib.decode_attn_mx, False, (q2, k2, v2, k_payload, k_scale, v_payload,
+                                    v_scale, cos, sin, pos_t),
+        B, T, Hq, Hkv, Smax, scale, st)
 
 
 def mx_kv_store(k: torch.Tensor, v: torch.Tensor, k_payload: torch.Tensor,
@@ -1420,9 +1456,6 @@ def mx_kv_store(k: torch.Tensor, v: torch.Tensor, k_payload: torch.Tensor,
 # chunked prefill)
 # ---------------------------------------------------------------------------
 
-_CA_TMIN, _CA_TMAX = 2, 8   # CA_TMIN / CA_TMAX of csrc/chunk_attn.hip
-
-
 def chunk_attn_available() -> bool:
     lib = _load()
     return lib is not None and hasattr(lib, "chunk_attn")
@@ -1431,63 +1464,6 @@ def chunk_attn_available() -> bool:
 def chunk_attn_mx_available() -> bool:
     lib = _load()
     return lib is not None and hasattr(lib, "chunk_attn_mx")
-
-
-def _chunk_attn_check(who, q3, k3, v3, cos, sin, pos_t, B, Hq, Hkv, Smax,
-                      dev):
-    """Everything but the cache, for both chunk kernels.  Returns T and the
-    element strides (q batch, q token, kv batch, kv token)."""
-    D = _DA_D
-    if Hkv < 1 or Hq % Hkv or Hq // Hkv not in (1, 2, 4, 8):
-        raise ValueError(f"{who}: Hq={Hq}, Hkv={Hkv} outside the kernel "
-                         f"contract (GQA rep 1/2/4/8)")
-    if q3.dim() != 3 or not _CA_TMIN <= q3.shape[1] <= _CA_TMAX:
-        raise ValueError(f"{who}: q3 {tuple(q3.shape)} must be (B, T, Hq*128) "
-                         f"with {_CA_TMIN} <= T <= {_CA_TMAX}")
-    T = q3.shape[1]
-    if Smax < T:
-        raise ValueError(f"{who}: a cache of {Smax} rows cannot take {T} "
-                         f"tokens")
-    for name, t, width in (("q3", q3, Hq * D), ("k3", k3, Hkv * D),
-                           ("v3", v3, Hkv * D)):
-        if t.dtype != torch.bfloat16 or t.device != dev or t.dim() != 3 \
-                or tuple(t.shape) != (B, T, width) or t.stride(2) != 1 \
-                or t.stride(1) < width or t.data_ptr() % 16 \
-                or t.stride(0) % 8 or t.stride(1) % 8:
-            raise ValueError(f"{who}: {name} must be a 16-byte aligned bf16 "
-                             f"({B}, {T}, {width}) tensor on {dev} with a "
-                             f"dense last dim and row strides that hold a "
-                             f"row, got {t.dtype} {tuple(t.shape)} strides "
-                             f"{t.stride()} on {t.device}")
-    if k3.stride() != v3.stride():
-        raise ValueError(f"{who}: k3 and v3 must share their strides, got "
-                         f"{k3.stride()} and {v3.stride()}")
-    for name, t in (("cos", cos), ("sin", sin)):
-        _mx_check_dense(f"{who}: {name}", t, torch.float32)
-        if t.device != dev or t.dim() != 2 or t.shape[1] != D // 2 \
-                or t.shape[0] < Smax or t.data_ptr() % 16:
-            raise ValueError(f"{who}: {name} {tuple(t.shape)} on {t.device} "
-                             f"must be (>= {Smax}, {D // 2}) on {dev}: the "
-                             f"RoPE table covers the cache")
-    if pos_t.dtype != torch.int64 or pos_t.device != dev \
-            or pos_t.numel() != 1:
-        raise ValueError(f"{who}: pos_t must be one int64 on {dev}, got "
-                         f"{pos_t.dtype} {tuple(pos_t.shape)} on "
-                         f"{pos_t.device}")
-    return T, (int(q3.stride(0)), int(q3.stride(1)), int(k3.stride(0)),
-               int(k3.stride(1)))
-
-
-def _chunk_attn_workspace(B, T, Hq, Hkv, dev):
-    """(part_o, part_ml, out); static shapes from the caching allocator, so
-    the three launches are hipGraph-capturable."""
-    R = Hq // Hkv * T
-    part_o = torch.empty(B * Hkv * _DA_SPLIT, R, _DA_D, dtype=torch.float32,
-                         device=dev)
-    part_ml = torch.empty(B * Hkv * _DA_SPLIT, R, 2, dtype=torch.float32,
-                          device=dev)
-    out = torch.empty(B, T, Hq * _DA_D, dtype=torch.bfloat16, device=dev)
-    return part_o, part_ml, out
 
 
 def chunk_attn_step(q3: torch.Tensor, k3: torch.Tensor, v3: torch.Tensor,
@@ -1510,32 +1486,12 @@ def chunk_attn_step(q3: torch.Tensor, k3: torch.Tensor, v3: torch.Tensor,
     who = "chunk_attn_step"
     if not chunk_attn_available():
         raise RuntimeError("nxd_ops library has no chunk_attn — rebuild")
-    for name, t in (("kcache", kcache), ("vcache", vcache)):
-        if t.dtype != torch.bfloat16 or t.dim() != 4 \
-                or t.shape[-1] != _DA_D or not t.is_cuda \
-                or not t.is_contiguous():
-            raise ValueError(f"{who}: {name} must be a contiguous bf16 "
-                             f"(B, Hkv, Smax, 128) GPU cache, got {t.dtype} "
-                             f"{tuple(t.shape)} on {t.device}")
-    if vcache.shape != kcache.shape or vcache.device != kcache.device \
-            or kcache.shape[1] != Hkv or min(kcache.shape) < 1:
-        raise ValueError(f"{who}: kcache {tuple(kcache.shape)} and vcache "
-                         f"{tuple(vcache.shape)} must be one non-empty shape "
-                         f"on one GPU with Hkv={Hkv} heads")
-    B, _, Smax, _ = kcache.shape
-    dev = kcache.device
-    T, st = _chunk_attn_check(who, q3, k3, v3, cos, sin, pos_t, B, Hq, Hkv,
-                              Smax, dev)
-    part_o, part_ml, out = _chunk_attn_workspace(B, T, Hq, Hkv, dev)
-    rc = lib.chunk_attn(_ptr(q3), _ptr(k3), _ptr(v3), _ptr(kcache),
-                        _ptr(vcache), _ptr(cos), _ptr(sin), _ptr(pos_t),
-                        _ptr(part_o), _ptr(part_ml), _ptr(out), B, T, Hq, Hkv,
-                        Smax, ctypes.c_float(scale),
-                        *(ctypes.c_long(s) for s in st), _stream())
-    if rc != 0:
-        raise ValueError(f"chunk_attn rejected B={B}, T={T}, Hq={Hq}, "
-                         f"Hkv={Hkv}, Smax={Smax}, strides {st}")
-    return out
+    B, Smax = _decode_attn_check_cache(who, kcache, vcache, Hkv)
+    T, st = _decode_attn_check(who, True, q3, k3, v3, cos, sin, pos_t, B, Hq,
+                               Hkv, Smax, kcache.device)
+    return _decode_attn_launch(
+        lib.chunk_attn, True, (q3, k3, v3, kcache, vcache, cos, sin, pos_t),
+        B, T, Hq, Hkv, Smax, scale, st)
 
 
 def chunk_attn_mx_step(q3: torch.Tensor, k3: torch.Tensor, v3: torch.Tensor,
@@ -1559,16 +1515,9 @@ def chunk_attn_mx_step(q3: torch.Tensor, k3: torch.Tensor, v3: torch.Tensor,
         raise ValueError(f"{who}: cache {tuple(k_payload.shape)} on {dev} "
                          f"with Hkv={Hkv} outside the kernel contract "
                          f"(D = 128, GPU)")
-    T, st = _chunk_attn_check(who, q3, k3, v3, cos, sin, pos_t, B, Hq, Hkv,
-                              Smax, dev)
-    part_o, part_ml, out = _chunk_attn_workspace(B, T, Hq, Hkv, dev)
-    rc = lib.chunk_attn_mx(_ptr(q3), _ptr(k3), _ptr(v3), _ptr(k_payload),
-                           _ptr(k_scale), _ptr(v_payload), _ptr(v_scale),
-                           _ptr(cos), _ptr(sin), _ptr(pos_t), _ptr(part_o),
-                           _ptr(part_ml), _ptr(out), B, T, Hq, Hkv, Smax,
-                           ctypes.c_float(scale),
-                           *(ctypes.c_long(s) for s in st), _stream())
-    if rc != 0:
-        raise ValueError(f"chunk_attn_mx rejected B={B}, T={T}, Hq={Hq}, "
-                         f"Hkv={Hkv}, Smax={Smax}, strides {st}")
-    return out
+    T, st = _decode_attn_check(who, True, q3, k3, v3, cos, sin, pos_t, B, Hq,
+                               Hkv, Smax, dev)
+    return _decode_attn_launch(
+        lib.chunk_attn_mx, True, (q3, k3, v3, k_payload, k_scale, v_payload,
+                                  v_scale, cos, sin, pos_t),
+        B, T, Hq, Hkv, Smax, scale, st)

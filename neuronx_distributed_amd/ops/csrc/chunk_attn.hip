@@ -24,8 +24,8 @@
 //      transposed read of the LDS image.  The four waves of a workgroup
 //      take the tiles of the split round-robin, each with its own (m, l, O);
 //      they merge in LDS and write one fp32 partial per split.
-//   3. chunk_attn_merge: log-sum-exp over the DA_SPLIT partials, bf16 out
-//      (B, T, Hq * 128).
+//   3. decode_attn_merge (decode_attn.hip): log-sum-exp over the DA_SPLIT
+//      partials, bf16 out (B, T, Hq * 128).
 //
 // Rows at or beyond n = min(pos + T, Smax), and the unfilled part of the last
 // tile, are ZEROED while staging (K and V) and their address is clamped to
@@ -75,7 +75,6 @@
 #define CA_WAVE_B (2 * CA_IMG_B)            // K image, then V image
 #define CA_LDS_B (DA_WAVES * CA_WAVE_B)     // 65536 B
 #define CA_OPAD 132                         // floats per row of the merge tile
-#define CA_NEG (-1e30f)
 
 // the device position, clamped to [-CA_TMAX, Smax]: outside that range no
 // row is written and the set of rows attended does not change any more
@@ -326,7 +325,7 @@ chunk_attn_part(const short* __restrict__ qin, const void* __restrict__ kc,
   float m_run[NQB], l_run[NQB];
 #pragma unroll
   for (int qb = 0; qb < NQB; ++qb) {
-    m_run[qb] = CA_NEG;
+    m_run[qb] = DA_NEG;
     l_run[qb] = 0.f;
   }
   const float s2 = scale * DA_LOG2E;
@@ -375,9 +374,9 @@ chunk_attn_part(const short* __restrict__ qin, const void* __restrict__ kc,
       if (need_mask) {
 #pragma unroll
         for (int r = 0; r < 16; ++r)
-          sc[r] = kv0 + acc_row(r, hi) > lim[qb] ? CA_NEG : sc[r];
+          sc[r] = kv0 + acc_row(r, hi) > lim[qb] ? DA_NEG : sc[r];
       }
-      float mt = CA_NEG;
+      float mt = DA_NEG;
 #pragma unroll
       for (int r = 0; r < 16; ++r) mt = fmaxf(mt, sc[r]);
       mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
@@ -427,7 +426,7 @@ chunk_attn_part(const short* __restrict__ qin, const void* __restrict__ kc,
   __syncthreads();
 #pragma unroll
   for (int qb = 0; qb < NQB; ++qb) {
-    float M = CA_NEG;
+    float M = DA_NEG;
 #pragma unroll
     for (int w = 0; w < DA_WAVES; ++w)
       M = fmaxf(M, mlm[w * 32 * NQB + 32 * qb + col]);
@@ -459,7 +458,7 @@ chunk_attn_part(const short* __restrict__ qin, const void* __restrict__ kc,
         *(const f4v*)(obuf + rho * CA_OPAD + 4 * c4);
   }
   if (tid < R) {
-    float M = CA_NEG;
+    float M = DA_NEG;
 #pragma unroll
     for (int w = 0; w < DA_WAVES; ++w) M = fmaxf(M, mlm[w * 32 * NQB + tid]);
     float L = 0.f;
@@ -467,45 +466,8 @@ chunk_attn_part(const short* __restrict__ qin, const void* __restrict__ kc,
     for (int w = 0; w < DA_WAVES; ++w)
       L += mll[w * 32 * NQB + tid] *
            __builtin_amdgcn_exp2f(mlm[w * 32 * NQB + tid] - M);
-    part_ml[((long)wg * R + tid) * 2 + 0] = L > 0.f ? M : CA_NEG;
+    part_ml[((long)wg * R + tid) * 2 + 0] = L > 0.f ? M : DA_NEG;
     part_ml[((long)wg * R + tid) * 2 + 1] = L;
-  }
-}
-
-// ---------------------------------------------------------------------------
-// 3. merge: block (pair, token); wave g takes head g, g + 4, a lane 2 dims
-// ---------------------------------------------------------------------------
-template <int REP>
-__global__ void __launch_bounds__(256)
-chunk_attn_merge(const float* __restrict__ part_o,
-                 const float* __restrict__ part_ml, short* __restrict__ outp,
-                 int T, int Hq, int Hkv) {
-  const int pair = blockIdx.x;
-  const int tok = blockIdx.y;
-  const int kvh = pair % Hkv;
-  const int b = pair / Hkv;
-  const int lane = threadIdx.x & 63;
-  const int wid = threadIdx.x >> 6;
-  const int R = REP * T;
-  for (int g = wid; g < REP; g += 4) {
-    const int rho = tok * REP + g;
-    float m_g = CA_NEG;
-#pragma unroll
-    for (int sp = 0; sp < DA_SPLIT; ++sp)
-      m_g = fmaxf(m_g, part_ml[(((long)pair * DA_SPLIT + sp) * R + rho) * 2]);
-    float l_g = 0.f, a0 = 0.f, a1 = 0.f;
-#pragma unroll
-    for (int sp = 0; sp < DA_SPLIT; ++sp) {
-      const long idx = ((long)pair * DA_SPLIT + sp) * R + rho;
-      const float sw = __builtin_amdgcn_exp2f(part_ml[idx * 2] - m_g);
-      l_g += part_ml[idx * 2 + 1] * sw;
-      const float* po = part_o + idx * DA_D;
-      a0 += po[2 * lane] * sw;
-      a1 += po[2 * lane + 1] * sw;
-    }
-    const float inv = l_g > 0.f ? 1.f / l_g : 0.f;
-    *(uint*)(outp + (((long)b * T + tok) * Hq + kvh * REP + g) * DA_D +
-             2 * lane) = pack_bf16x2(a0 * inv, a1 * inv);
   }
 }
 
@@ -542,32 +504,22 @@ static int ca_launch(const void* q, const void* k, const void* v, void* kc,
   if (((uintptr_t)kc | (uintptr_t)vc) % 16 ||
       (MX && ((uintptr_t)ksc | (uintptr_t)vsc) % 4))
     return 1;
-  const int rep = Hq / Hkv;
   chunk_attn_append<MX><<<B * Hkv * T, 128, 0, stream>>>(
       (const short*)k, (const short*)v, kc, (uint8_t*)ksc, vc, (uint8_t*)vsc,
       (const float*)cosp, (const float*)sinp, (const long*)pos_ptr, T, Hkv,
       Smax, kv_bs, kv_ts);
-#define LAUNCH(R, NQB)                                                       \
-  chunk_attn_part<R, NQB, MX><<<B * Hkv * DA_SPLIT, DA_WAVES * 64, 0,        \
-                                stream>>>(                                   \
-      (const short*)q, kc, (const uint8_t*)ksc, vc, (const uint8_t*)vsc,     \
-      (const float*)cosp, (const float*)sinp, (const long*)pos_ptr,          \
-      (float*)part_o, (float*)part_ml, T, Hkv, Smax, scale, q_bs, q_ts)
-#define MERGE(R)                                                             \
-  chunk_attn_merge<R><<<dim3(B * Hkv, T), 256, 0, stream>>>(                 \
-      (const float*)part_o, (const float*)part_ml, (short*)outp, T, Hq, Hkv)
-  switch (rep) {
-    case 1: LAUNCH(1, 1); MERGE(1); break;
-    case 2: LAUNCH(2, 1); MERGE(2); break;
-    case 4: LAUNCH(4, 1); MERGE(4); break;
-    default:
-      if (rep * T <= 32) LAUNCH(8, 1); else LAUNCH(8, 2);
-      MERGE(8);
-      break;
-  }
-#undef LAUNCH
-#undef MERGE
-  return 0;
+  da_for_rep(Hq / Hkv, [&](auto rep) {
+    constexpr int R = decltype(rep)::value;
+    auto part = chunk_attn_part<R, 1, MX>;  // two query blocks: rep 8 only
+    if constexpr (R == 8)
+      if (R * T > 32) part = chunk_attn_part<R, 2, MX>;
+    part<<<B * Hkv * DA_SPLIT, DA_WAVES * 64, 0, stream>>>(
+        (const short*)q, kc, (const uint8_t*)ksc, vc, (const uint8_t*)vsc,
+        (const float*)cosp, (const float*)sinp, (const long*)pos_ptr,
+        (float*)part_o, (float*)part_ml, T, Hkv, Smax, scale, q_bs, q_ts);
+  });
+  return decode_attn_merge_launch(part_o, part_ml, outp, B, T, Hq, Hkv,
+                                  stream);
 }
 
 // q_bs/q_ts, kv_bs/kv_ts: element strides (batch, token) of q and of k = v.

@@ -17,7 +17,8 @@
 // pos/DA_SPLIT row chunk, merges its quarter-wave partials in LDS, writes
 // one fp32 partial (m, l, o[REP][128]) to workspace; split 0 also
 // appends the new K/V row and adds its term.  Phase 2
-// (decode_attn_merge) log-sum-exp-combines the splits -> bf16 out.
+// (decode_attn_merge) log-sum-exp-combines the splits -> bf16 out; it is
+// also phase 2 of decode_attn_mx.hip and, with T tokens, of chunk_attn.hip.
 //
 // Constants, layouts and every phase-1 piece but the walk over the cache
 // are in decode_attn_common.h, shared with decode_attn_mx.hip.
@@ -129,63 +130,57 @@ decode_attn_part(const short* __restrict__ qlin,
   da_merge_store<REP>(c, merge_o, merge_ml, part_o, part_ml);
 }
 
+// Phase 2, block (pair, token): wave w takes heads w, w + 4, a lane 2 dims of
+// workspace row rho = tok * REP + g of each split.
 template <int REP>
 __global__ void __launch_bounds__(256)
 decode_attn_merge(const float* __restrict__ part_o,
-                     const float* __restrict__ part_ml,
-                     short* __restrict__ outp, int B, int Hq, int Hkv) {
+                  const float* __restrict__ part_ml, short* __restrict__ outp,
+                  int T, int Hq, int Hkv) {
   const int pair = blockIdx.x;
+  const int tok = blockIdx.y;
   const int kvh = pair % Hkv;
   const int b = pair / Hkv;
-  const int qh0 = kvh * REP;
   const int lane = threadIdx.x & 63;
   const int wid = threadIdx.x >> 6;
+  const int R = REP * T;
   for (int g = wid; g < REP; g += 4) {
-    float m_g = -1e30f;
+    const int rho = tok * REP + g;
+    float m_g = DA_NEG;
 #pragma unroll
     for (int sp = 0; sp < DA_SPLIT; ++sp)
-      m_g = fmaxf(m_g,
-                  part_ml[(((long)pair * DA_SPLIT + sp) * REP + g) * 2]);
+      m_g = fmaxf(m_g, part_ml[(((long)pair * DA_SPLIT + sp) * R + rho) * 2]);
     float l_g = 0.f, a0 = 0.f, a1 = 0.f;
 #pragma unroll
     for (int sp = 0; sp < DA_SPLIT; ++sp) {
-      const long idx = ((long)pair * DA_SPLIT + sp) * REP + g;
-      const float mw = part_ml[idx * 2];
-      const float sw = __builtin_amdgcn_exp2f(mw - m_g);
+      const long idx = ((long)pair * DA_SPLIT + sp) * R + rho;
+      const float sw = __builtin_amdgcn_exp2f(part_ml[idx * 2] - m_g);
       l_g += part_ml[idx * 2 + 1] * sw;
       const float* po = part_o + idx * DA_D;
       a0 += po[2 * lane] * sw;
       a1 += po[2 * lane + 1] * sw;
     }
-    float inv = 1.f / l_g;
-    uint outpair = pack_bf16x2(a0 * inv, a1 * inv);
-    *(uint*)(outp + (long)b * Hq * DA_D + (qh0 + g) * DA_D + 2 * lane) =
-        outpair;
+    const float inv = l_g > 0.f ? 1.f / l_g : 0.f;
+    *(uint*)(outp + (((long)b * T + tok) * Hq + kvh * REP + g) * DA_D +
+             2 * lane) = pack_bf16x2(a0 * inv, a1 * inv);
   }
 }
 
-// Phase 2 for every phase-1 kernel (this file's and decode_attn_mx.hip's):
-// the fp32 partials carry no trace of the cache format.  Returns non-zero,
-// launching nothing, unless Hq / Hkv is 1, 2, 4 or 8.
+// Phase 2 for every phase-1 kernel of the family (this file's,
+// decode_attn_mx.hip's and chunk_attn.hip's): the fp32 partials carry no
+// trace of the cache format.  Returns non-zero, launching nothing, unless
+// Hq / Hkv is 1, 2, 4 or 8.
 extern "C" int decode_attn_merge_launch(const void* part_o,
                                         const void* part_ml, void* outp,
-                                        int B, int Hq, int Hkv,
+                                        int B, int T, int Hq, int Hkv,
                                         hipStream_t stream) {
-  if (B < 1 || Hkv < 1 || Hq % Hkv != 0) return 1;
-  dim3 grid2(B * Hkv);
-#define LAUNCH(R)                                                        \
-  decode_attn_merge<R><<<grid2, 256, 0, stream>>>(                       \
-      (const float*)part_o, (const float*)part_ml, (short*)outp, B, Hq,  \
-      Hkv)
-  switch (Hq / Hkv) {
-    case 1: LAUNCH(1); break;
-    case 2: LAUNCH(2); break;
-    case 4: LAUNCH(4); break;
-    case 8: LAUNCH(8); break;
-    default: return 1;
-  }
-#undef LAUNCH
-  return 0;
+  if (B < 1 || T < 1 || Hkv < 1 || Hq % Hkv != 0) return 1;
+  return !da_for_rep(Hq / Hkv, [&](auto rep) {
+    decode_attn_merge<decltype(rep)::value>
+        <<<dim3(B * Hkv, T), 256, 0, stream>>>(
+            (const float*)part_o, (const float*)part_ml, (short*)outp, T, Hq,
+            Hkv);
+  });
 }
 
 // Returns non-zero, launching nothing, outside da_launch_ok's contract.
@@ -197,19 +192,14 @@ extern "C" int decode_attn(const void* qlin, const void* klin,
                            float scale, int qstride, int kvstride,
                            hipStream_t stream) {
   if (!da_launch_ok(B, Hq, Hkv, Smax, qstride, kvstride)) return 1;
-  dim3 grid1(B * Hkv * DA_SPLIT);
-#define LAUNCH(R)                                                        \
-  decode_attn_part<R><<<grid1, DA_WAVES * 64, 0, stream>>>(              \
-      (const short*)qlin, (const short*)klin, (const short*)vlin,        \
-      (short*)kcache, (short*)vcache, (const float*)cosp,                \
-      (const float*)sinp, (const long*)pos_ptr, (float*)part_o,          \
-      (float*)part_ml, B, Hq, Hkv, Smax, scale, qstride, kvstride)
-  switch (Hq / Hkv) {
-    case 1: LAUNCH(1); break;
-    case 2: LAUNCH(2); break;
-    case 4: LAUNCH(4); break;
-    default: LAUNCH(8); break;
-  }
-#undef LAUNCH
-  return decode_attn_merge_launch(part_o, part_ml, outp, B, Hq, Hkv, stream);
+  da_for_rep(Hq / Hkv, [&](auto rep) {
+    decode_attn_part<decltype(rep)::value>
+        <<<B * Hkv * DA_SPLIT, DA_WAVES * 64, 0, stream>>>(
+            (const short*)qlin, (const short*)klin, (const short*)vlin,
+            (short*)kcache, (short*)vcache, (const float*)cosp,
+            (const float*)sinp, (const long*)pos_ptr, (float*)part_o,
+            (float*)part_ml, B, Hq, Hkv, Smax, scale, qstride, kvstride);
+  });
+  return decode_attn_merge_launch(part_o, part_ml, outp, B, 1, Hq, Hkv,
+                                  stream);
 }

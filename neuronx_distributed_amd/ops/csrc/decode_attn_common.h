@@ -17,20 +17,38 @@
 // split without rows.  D = 128.  No atomics.
 #pragma once
 
+#include <type_traits>
+
 #include "common.h"
 
 #define DA_D 128
+#define DA_NEG (-1e30f)            // m of a softmax state that holds no row
 #define DA_LOG2E 1.4426950408889634f
 #define DA_WAVES 4                 // waves per workgroup
 #define DA_SPLIT 4                 // KV-range splits per (batch, kv-head)
 #define DA_SLOTS (4 * DA_WAVES)    // quarter-wave partials merged per WG
 
-// Phase 2 (decode_attn.hip), built for the same DA_SPLIT.  Returns non-zero,
-// launching nothing, unless Hq / Hkv is 1, 2, 4 or 8.
+// Phase 2 (decode_attn.hip) for every phase-1 kernel of the family, built for
+// the same DA_SPLIT: T tokens per sequence, workspace rows t * rep + g, out
+// (B, T, Hq * D) bf16.  Returns non-zero, launching nothing, unless Hq / Hkv
+// is 1, 2, 4 or 8.
 extern "C" int decode_attn_merge_launch(const void* part_o,
                                         const void* part_ml, void* outp,
-                                        int B, int Hq, int Hkv,
+                                        int B, int T, int Hq, int Hkv,
                                         hipStream_t stream);
+
+// Host: f(std::integral_constant<int, REP>) for rep = REP in {1, 2, 4, 8};
+// false, calling nothing, for any other rep.
+template <class F>
+static inline bool da_for_rep(int rep, F&& f) {
+  switch (rep) {
+    case 1: f(std::integral_constant<int, 1>{}); return true;
+    case 2: f(std::integral_constant<int, 2>{}); return true;
+    case 4: f(std::integral_constant<int, 4>{}); return true;
+    case 8: f(std::integral_constant<int, 8>{}); return true;
+  }
+  return false;
+}
 
 // The launch contract of both phase-1 kernels: rep in {1, 2, 4, 8}, positive
 // sizes, row strides that hold a row, a grid that fits an int.
@@ -107,7 +125,7 @@ __device__ __forceinline__ void da_init_state(const float (&qr)[REP][DA_D],
     for (int j = 0; j < 8; ++j) qv[g][j] = qr[g][8 * hl + j];
 #pragma unroll
   for (int g = 0; g < REP; ++g) {
-    m_run[g] = -1e30f;
+    m_run[g] = DA_NEG;
     l_run[g] = 0.f;
 #pragma unroll
     for (int j = 0; j < 8; ++j) ov[g][j] = 0.f;
@@ -182,7 +200,7 @@ __device__ __forceinline__ void da_merge_store(
     float* part_ml) {
   const int nslot = DA_SLOTS + (c.s == 0 ? 1 : 0);
   for (int g = c.wid; g < REP; g += DA_WAVES) {
-    float m_g = -1e30f;
+    float m_g = DA_NEG;
     for (int w = 0; w < nslot; ++w) m_g = fmaxf(m_g, merge_ml[w][g][0]);
     float l_g = 0.f, a0 = 0.f, a1 = 0.f;
     for (int w = 0; w < nslot; ++w) {
@@ -195,7 +213,7 @@ __device__ __forceinline__ void da_merge_store(
     po[2 * c.lane] = a0;
     po[2 * c.lane + 1] = a1;
     if (c.lane == 0) {
-      part_ml[((long)c.wg * REP + g) * 2 + 0] = l_g > 0.f ? m_g : -1e30f;
+      part_ml[((long)c.wg * REP + g) * 2 + 0] = l_g > 0.f ? m_g : DA_NEG;
       part_ml[((long)c.wg * REP + g) * 2 + 1] = l_g;
     }
   }

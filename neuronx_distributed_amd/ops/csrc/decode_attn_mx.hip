@@ -231,22 +231,17 @@ extern "C" int decode_attn_mx(const void* qlin, const void* klin,
                               int Hq, int Hkv, int Smax, float scale,
                               int qstride, int kvstride, hipStream_t stream) {
   if (!da_launch_ok(B, Hq, Hkv, Smax, qstride, kvstride)) return 1;
-  dim3 grid1(B * Hkv * DA_SPLIT);
-#define LAUNCH(R)                                                          \
-  decode_attn_mx_part<R><<<grid1, DA_WAVES * 64, 0, stream>>>(             \
-      (const short*)qlin, (const short*)klin, (const short*)vlin,          \
-      (uint8_t*)kpay, (uint8_t*)ksc, (uint8_t*)vpay, (uint8_t*)vsc,        \
-      (const float*)cosp, (const float*)sinp, (const long*)pos_ptr,        \
-      (float*)part_o, (float*)part_ml, B, Hq, Hkv, Smax, scale, qstride,   \
-      kvstride)
-  switch (Hq / Hkv) {
-    case 1: LAUNCH(1); break;
-    case 2: LAUNCH(2); break;
-    case 4: LAUNCH(4); break;
-    default: LAUNCH(8); break;
-  }
-#undef LAUNCH
-  return decode_attn_merge_launch(part_o, part_ml, outp, B, Hq, Hkv, stream);
+  da_for_rep(Hq / Hkv, [&](auto rep) {
+    decode_attn_mx_part<decltype(rep)::value>
+        <<<B * Hkv * DA_SPLIT, DA_WAVES * 64, 0, stream>>>(
+            (const short*)qlin, (const short*)klin, (const short*)vlin,
+            (uint8_t*)kpay, (uint8_t*)ksc, (uint8_t*)vpay, (uint8_t*)vsc,
+            (const float*)cosp, (const float*)sinp, (const long*)pos_ptr,
+            (float*)part_o, (float*)part_ml, B, Hq, Hkv, Smax, scale, qstride,
+            kvstride);
+  });
+  return decode_attn_merge_launch(part_o, part_ml, outp, B, 1, Hq, Hkv,
+                                  stream);
 }
 
 // ---------------------------------------------------------------------------

@@ -637,7 +637,7 @@ def test_model_chunk_matches_reference(kv_format, monkeypatch):
     """model(chunk, pos_offset=tensor), the fused kernels, against the same
     weights on another path: for the bf16 cache the int-position forward
     (rectangular attention over the prefix), for mxfp8 the eager chain of
-    LlamaAttention._chunk_step itself (kernels made unavailable).
+    LlamaAttention._cached_step itself (kernels made unavailable).
 
     Cache rows: layer 0 of both runs sees identical hidden states, so its V
     rows are bit-equal and its K rows within one bf16 ulp (MX: the same

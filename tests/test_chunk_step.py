@@ -1,11 +1,13 @@
 """The multi-token decode step with a device position, on the CPU in fp32
-(models/llama.py LlamaAttention._chunk_step, the eager chain that is also the
-reference of the fused GPU kernels of test_chunk_attn_gpu.py):
+(models/llama.py LlamaAttention._cached_step, the eager chain that is also
+the reference of the fused GPU kernels of test_chunk_attn_gpu.py):
 
 * a tensor-position forward of S in {2, 5, 8} tokens equals the int-position
   forward on a copy of the caches, logits and cache contents, for KVCache and
   MXKVCache,
-* S == 1 with a tensor position is still exactly _decode_step,
+* S == 1 with a tensor position is still exactly _cached_step,
+* eight one-token steps into a RollingKVCache (sliding window 4) equal the
+  int-position steps,
 * RollingKVCache refuses a multi-token tensor-position update,
 * speculative_generate / medusa_generate with fused_verify=True return the
   tokens of the default path and of plain greedy generation.
@@ -78,7 +80,7 @@ def test_chunk_forward_equals_int_position(kv_format):
 
 
 def _single_worker(rank, world):
-    """S == 1: forward() still hands a tensor position to _decode_step."""
+    """S == 1: forward() still hands a tensor position to _cached_step."""
     from neuronx_distributed_amd.parallel import parallel_state as ps
 
     ps.initialize_model_parallel(tensor_model_parallel_size=1)
@@ -97,7 +99,7 @@ def _single_worker(rank, world):
         got = attn(hidden, cos, sin, pos_t, c1)
         q, k, v = attn.qkv_proj(hidden)
         shp = lambda t, h: t.reshape(B, 1, h, attn.head_dim)  # noqa: E731
-        want = attn._decode_step(shp(q, attn.num_heads_local),
+        want = attn._cached_step(shp(q, attn.num_heads_local),
                                  shp(k, attn.num_kv_local),
                                  shp(v, attn.num_kv_local), cos, sin, pos_t,
                                  c2, False)
@@ -109,6 +111,41 @@ def _single_worker(rank, world):
 
 def test_single_token_tensor_position_unchanged():
     run_distributed(_single_worker, world_size=1)
+
+
+def _rolling_worker(rank, world):
+    """The rolling branch of the eager chain: slots masked by their global
+    position, and by the window, from a device position."""
+    from neuronx_distributed_amd.inference.kv_cache import RollingKVCache
+    from neuronx_distributed_amd.parallel import parallel_state as ps
+
+    ps.initialize_model_parallel(tensor_model_parallel_size=1)
+    cfg, model = _models(0, sliding_window=4)
+    B, P, Smax = 2, 6, 16
+    torch.manual_seed(4)
+    x = torch.randint(0, cfg.vocab_size, (B, P + 8))
+    with torch.no_grad():
+        c_t = _caches(cfg, B, Smax, None, window=4)
+        assert all(type(c) is RollingKVCache for c in c_t)
+        # the int-position steps: a plain cache, windowed by the attention
+        # (a rolling cache takes an int position only for its prefill)
+        c_i = _caches(cfg, B, Smax, None)
+        model(x[:, :P], kv_caches=c_t, pos_offset=0)
+        model(x[:, :P], kv_caches=c_i, pos_offset=0)
+        for i in range(P, P + 8):   # the window wraps twice
+            tok = x[:, i:i + 1]
+            got = model(tok, kv_caches=c_t, pos_offset=torch.tensor([i]))
+            want = model(tok, kv_caches=c_i, pos_offset=i)
+            assert got.shape == want.shape == (B, 1, cfg.vocab_size)
+            assert torch.allclose(got, want, atol=1e-5, rtol=1e-5), \
+                (i, (got - want).abs().max())
+            for c in c_t:   # the slots hold the last four positions
+                assert sorted(c.slot_pos.tolist()) == list(range(i - 3, i + 1))
+    return True
+
+
+def test_rolling_single_token_tensor_position():
+    run_distributed(_rolling_worker, world_size=1)
 
 
 def test_rolling_cache_refuses_chunk():
@@ -158,13 +195,14 @@ def _spec_worker(rank, world, kv_format):
 
     seen = []
     attn_cls = type(target.model.layers[0].self_attn)
-    real = attn_cls._chunk_step
+    real = attn_cls._cached_step
 
     def spy(self, q, *a, **kw):
-        seen.append(q.shape[1])
+        if q.shape[1] > 1:   # one-token decode steps take the method too
+            seen.append(q.shape[1])
         return real(self, q, *a, **kw)
 
-    attn_cls._chunk_step = spy
+    attn_cls._cached_step = spy
     try:
         ref = generate(target, x, max_new_tokens=12, kv_format=kv_format)
         assert not seen
@@ -192,7 +230,7 @@ def _spec_worker(rank, world, kv_format):
         if kv_format is None:
             assert torch.equal(out, generate(target, x, max_new_tokens=10))
     finally:
-        attn_cls._chunk_step = real
+        attn_cls._cached_step = real
     return True
 
 
