@@ -5,7 +5,10 @@ engine ranks with torchrun and put the server on rank 0's feed.
 
   python examples/inference/serve.py --model llama3-8b --port 8000
   curl -X POST localhost:8000/generate -H 'Content-Type: application/json' \
-       -d '{"token_ids": [[1, 2, 3]], "max_new_tokens": 16}'
+       -d '{"token_ids": [[1, 2, 3], [4, 5]], "max_new_tokens": 16}'
+
+Prompts of one request may differ in length: they are right-padded and
+generated with one position per sequence (generate(prompt_lens=...)).
 """
 
 import argparse
@@ -51,6 +54,7 @@ def build_app(model_name: str = "test-d128"):
 
     class GenRequest(BaseModel):
         token_ids: list  # List[List[int]] — bring your own tokenizer
+        pad_token_id: int = 0
         max_new_tokens: int = 32
         do_sample: bool = False
         top_k: int = 50
@@ -58,13 +62,20 @@ def build_app(model_name: str = "test-d128"):
 
     @app.post("/generate")
     def gen(req: GenRequest):
-        x = torch.tensor(req.token_ids, dtype=torch.long, device=device)
+        lens = [len(row) for row in req.token_ids]
+        width = max(lens)
+        x = torch.tensor([list(row) + [req.pad_token_id] * (width - len(row))
+                          for row in req.token_ids],
+                         dtype=torch.long, device=device)
         sampler = Sampler(do_sample=req.do_sample, top_k=req.top_k,
                           temperature=req.temperature)
         with torch.no_grad():
             out = generate(model, x, max_new_tokens=req.max_new_tokens,
-                           sampler=sampler)
-        return {"token_ids": out[:, x.shape[1]:].tolist()}
+                           sampler=sampler, prompt_lens=lens,
+                           pad_token_id=req.pad_token_id)
+        # row b's new tokens follow its own prompt
+        return {"token_ids": [out[b, n:n + req.max_new_tokens].tolist()
+                              for b, n in enumerate(lens)]}
 
     @app.get("/health")
     def health():

@@ -33,9 +33,14 @@ class GraphDecoder:
     tokens — amortizing the inter-kernel replay gaps and the per-token
     host loop:
         toks = dec.step_block(next_tok)   # (B, N) token ids
+
+    ``start_pos``: an int, the position of the whole batch, or a length-B
+    sequence / (B,) tensor with one position per sequence (prompts of
+    different lengths); ``pos_t`` then has shape (B,) and every step advances
+    all of them by one.
     """
 
-    def __init__(self, model, kv_caches: List[KVCache], start_pos: int,
+    def __init__(self, model, kv_caches: List[KVCache], start_pos,
                  batch: int, device=None, steps_per_capture: int = 1):
         self.model = model
         self.caches = kv_caches
@@ -43,8 +48,13 @@ class GraphDecoder:
                                         torch.cuda.current_device())
         self.steps_per_capture = steps_per_capture
         self.step_in = torch.zeros(batch, 1, dtype=torch.long, device=device)
-        self.pos_t = torch.tensor([start_pos], dtype=torch.long,
-                                  device=device)
+        if isinstance(start_pos, int):
+            start_pos = [start_pos]
+        self.pos_t = torch.as_tensor(start_pos).to(
+            device=device, dtype=torch.long).reshape(-1).clone()
+        if self.pos_t.numel() not in (1, batch):
+            raise ValueError(f"start_pos holds {self.pos_t.numel()} "
+                             f"positions for a batch of {batch}")
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self.logits: Optional[torch.Tensor] = None
         self.tokens_out: Optional[torch.Tensor] = None

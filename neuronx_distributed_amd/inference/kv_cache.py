@@ -26,7 +26,16 @@ class KVCache:
         ``pos`` may be a device int64 tensor of shape (1,) (hipGraph
         decode): the write becomes index_copy_ and the FULL buffers are
         returned (attention masks by position — no dynamic shapes).  With
-        S > 1 the rows go to ``pos + arange(S)``."""
+        S > 1 the rows go to ``pos + arange(S)``.
+
+        A tensor of B > 1 positions is one per sequence: the rows go to
+        ``(b, :, pos[b] + s)``.  A sequence with ``pos[b] < 0`` or
+        ``pos[b] + S > max_seq`` is inactive and keeps its cache rows.  No
+        host sync either."""
+        if _is_ragged(pos, k_new.shape[0]):
+            _ragged_write(pos, (self.k, k_new.to(self.k.dtype)),
+                          (self.v, v_new.to(self.v.dtype)))
+            return self.k, self.v
         if isinstance(pos, torch.Tensor):
             pos = _chunk_rows(pos, k_new.shape[2])
             self.k.index_copy_(2, pos, k_new.to(self.k.dtype))
@@ -44,6 +53,28 @@ def _chunk_rows(pos: torch.Tensor, S: int) -> torch.Tensor:
     if S == 1:
         return pos
     return pos.reshape(1) + torch.arange(S, device=pos.device)
+
+
+def _is_ragged(pos, B: int) -> bool:
+    """One position per sequence: a tensor of B > 1 elements ((1,) with
+    B = 1 means the same in both readings and stays the shared position)."""
+    return isinstance(pos, torch.Tensor) and B > 1 and pos.numel() == B
+
+
+def _ragged_write(pos: torch.Tensor, *pairs) -> None:
+    """For each (buf (B,H,Smax,W), new (B,H,S,W)): new[b, :, s] into
+    buf[b, :, pos[b] + s] for the active sequences, those with all S rows in
+    [0, Smax).  An inactive one scatters back what its (clamped) rows hold,
+    so the write has one static shape and no host sync."""
+    B, _, S, _ = pairs[0][1].shape
+    Smax = pairs[0][0].shape[2]
+    pos = pos.reshape(B)
+    active = ((pos >= 0) & (pos + S <= Smax)).view(B, 1, 1, 1)
+    rows = pos.view(B, 1) + torch.arange(S, device=pos.device)
+    rows = rows.clamp(0, Smax - 1).view(B, 1, S, 1)
+    for buf, new in pairs:
+        idx = rows.expand(B, buf.shape[1], S, buf.shape[3])
+        buf.scatter_(2, idx, torch.where(active, new, buf.gather(2, idx)))
 
 
 KV_FORMATS = (None, "mxfp8")
@@ -102,6 +133,10 @@ class RollingKVCache(KVCache):
         return self.slot_pos
 
     def update(self, k_new: torch.Tensor, v_new: torch.Tensor, pos):
+        if isinstance(pos, torch.Tensor) and pos.numel() > 1:
+            raise NotImplementedError(
+                "RollingKVCache keeps one position for the whole batch; "
+                "per-sequence positions need a plain cache")
         if isinstance(pos, torch.Tensor):  # decode: one token
             if k_new.shape[2] != 1:
                 raise NotImplementedError(
@@ -192,6 +227,13 @@ class MXKVCache(KVCache):
     def update(self, k_new: torch.Tensor, v_new: torch.Tensor, pos):
         """Same signature and modes as :meth:`KVCache.update`; the returned
         K, V are dequantized copies in ``dtype`` (class docstring)."""
+        if _is_ragged(pos, k_new.shape[0]):
+            kq, ks = self._quantize(k_new)
+            vq, vs = self._quantize(v_new)
+            _ragged_write(pos, (self.k, kq), (self.k_scale, ks),
+                          (self.v, vq), (self.v_scale, vs))
+            return (self._dequantize(self.k, self.k_scale),
+                    self._dequantize(self.v, self.v_scale))
         if isinstance(pos, torch.Tensor):
             pos = _chunk_rows(pos, k_new.shape[2])
             kq, ks = self._quantize(k_new)

@@ -32,10 +32,97 @@ def _chunk_pos(pos: int, n_tokens: int, fused: bool, device):
     return pos
 
 
+def _speculative_per_sequence(target, draft, input_ids, max_new_tokens,
+                              spec_len, prompt_lens, pad_token_id, caches):
+    """speculative_generate(per_sequence=True): every sequence keeps its own
+    device position, accepts its own longest agreeing prefix and goes
+    inactive (position -1) once it has its ``max_new_tokens``."""
+    from .generation import check_prompt_lens, ragged_output
+
+    B, S = input_ids.shape
+    dev = input_ids.device
+    k = spec_len
+    if max_new_tokens < 1:
+        raise ValueError(f"per_sequence: max_new_tokens {max_new_tokens} must "
+                         f"be at least 1")
+    if not 1 <= k <= 7:
+        raise ValueError(f"per_sequence speculation verifies spec_len + 1 "
+                         f"tokens per device-position forward: spec_len {k} "
+                         f"must lie in [1, 7]")
+    lens = check_prompt_lens([S] * B if prompt_lens is None else prompt_lens,
+                             input_ids)
+    t_caches, d_caches = caches
+    rows = torch.arange(B, device=dev)
+
+    # both prefill the padded prompt; the draft's logits are unused and its
+    # first step rewrites row len_b - 1
+    t_logits = target(input_ids, kv_caches=t_caches, pos_offset=0)
+    draft(input_ids, kv_caches=d_caches, pos_offset=0)
+    tok = _greedy(t_logits[rows, lens - 1])
+    d_prev = input_ids[rows, lens - 1]
+
+    # row b's new tokens, written at its own column ``produced``; a round
+    # writes k + 1 of which the first j_b + 1 stand, the rest is overwritten
+    # by the next round or cut off at max_new_tokens
+    new = input_ids.new_full((B, max_new_tokens + k + 1), pad_token_id)
+    new[:, 0] = tok
+    produced = torch.ones(B, dtype=torch.long, device=dev)
+    pos = torch.where(produced < max_new_tokens, lens, -torch.ones_like(lens))
+    steps = torch.arange(k + 1, device=dev)
+    n_accepted = torch.zeros((), dtype=torch.long, device=dev)
+    n_row_rounds = 0
+
+    while True:
+        act = pos >= 0
+        n_act = int(act.sum())
+        if n_act == 0:
+            break
+        n_row_rounds += n_act
+
+        def at(off):  # an inactive row stays at -1
+            return torch.where(act, pos + off, pos)
+
+        # ---- draft proposes k tokens ---------------------------------
+        dl = draft(torch.stack([d_prev, tok], 1), kv_caches=d_caches,
+                   pos_offset=at(-1))
+        proposals = [_greedy(dl[:, -1, :])]
+        for i in range(1, k):
+            dl = draft(proposals[-1].unsqueeze(1), kv_caches=d_caches,
+                       pos_offset=at(i))
+            proposals.append(_greedy(dl[:, -1, :]))
+        dmat = torch.stack(proposals, dim=1)  # (B, k)
+
+        # ---- target verifies the chunk in one forward ----------------
+        chunk = torch.cat([tok.unsqueeze(1), dmat], dim=1)  # (B, k+1)
+        tmat = _greedy(target(chunk, kv_caches=t_caches, pos_offset=pos))
+
+        # per row: the longest agreeing prefix j_b; the j_b accepted tokens
+        # ARE the target's choices, so the row emits tmat[b, :j_b + 1]
+        j = (dmat == tmat[:, :-1]).long().cumprod(dim=1).sum(dim=1)  # (B,)
+        idx = produced.view(B, 1) + steps
+        idx = torch.where(act.view(B, 1), idx, steps.expand(B, -1))
+        new.scatter_(1, idx, torch.where(act.view(B, 1), tmat,
+                                         new.gather(1, idx)))
+        n_accepted += (j * act).sum()
+        d_prev = torch.where(j > 0, dmat.gather(
+            1, (j - 1).clamp(min=0).view(B, 1)).view(B), tok)
+        tok = tmat.gather(1, j.view(B, 1)).view(B)
+        produced = produced + (j + 1) * act
+        pos = torch.where(act & (produced < max_new_tokens), pos + j + 1,
+                          -torch.ones_like(pos))
+
+    tokens = ragged_output(input_ids, lens, new[:, :max_new_tokens],
+                           S + max_new_tokens, pad_token_id)
+    rate = int(n_accepted) / max(1, n_row_rounds * spec_len)
+    return tokens, rate
+
+
 @torch.no_grad()
 def speculative_generate(target, draft, input_ids: torch.Tensor,
                          max_new_tokens: int = 32, spec_len: int = 4,
-                         kv_format=None, fused_verify: bool = False):
+                         kv_format=None, fused_verify: bool = False,
+                         per_sequence: bool = False, prompt_lens=None,
+                         pad_token_id: int = 0):
     """Greedy speculative generation.  target/draft:
     LlamaForCausalLM-compatible; input_ids (B, S).  Returns
     (tokens (B, S+new), acceptance_rate).  ``kv_format``: the cache format
@@ -43,7 +130,19 @@ def speculative_generate(target, draft, input_ids: torch.Tensor,
     verify chunk and the draft's two-token step with a device position, i.e.
     through the fused multi-token decode attention (ops.chunk_attn_step /
     ops.chunk_attn_mx_step on GPU) instead of rectangular attention over the
-    prefix; chunks of more than 8 tokens keep the default path."""
+    prefix; chunks of more than 8 tokens keep the default path.
+
+    ``per_sequence``: acceptance per sequence instead of what the whole batch
+    agrees on.  Positions are a device (B,) tensor and every draft step and
+    verify chunk is a device-position forward (LlamaAttention._cached_step):
+    through the fused ragged kernels with ``fused_verify`` where the model
+    can take them, through its eager chain otherwise; spec_len <= 7.  A
+    sequence that has its ``max_new_tokens`` goes inactive.  The result is
+    laid out as by ``generate(prompt_lens=...)`` and the rate is accepted
+    tokens over (active sequence-rounds x spec_len).  ``prompt_lens``
+    (per_sequence only): lengths of right-padded prompts, as in generate."""
+    if prompt_lens is not None and not per_sequence:
+        raise ValueError("prompt_lens needs per_sequence=True")
     B, S = input_ids.shape
     dev = input_ids.device
 
@@ -61,6 +160,14 @@ def speculative_generate(target, draft, input_ids: torch.Tensor,
 
     t_caches = make_caches(target)
     d_caches = make_caches(draft)
+    if per_sequence:
+        from .. import ops
+
+        with ops.ragged_attn_step(fused_verify):
+            return _speculative_per_sequence(target, draft, input_ids,
+                                             max_new_tokens, spec_len,
+                                             prompt_lens, pad_token_id,
+                                             (t_caches, d_caches))
 
     # prefill both; the draft's prefill logits are unused
     t_logits = target(input_ids, kv_caches=t_caches, pos_offset=0)
@@ -98,7 +205,7 @@ def speculative_generate(target, draft, input_ids: torch.Tensor,
         tmat = _greedy(tl)  # (B, k+1): target choice AFTER each prefix
 
         # longest agreeing prefix (whole batch must agree to advance a
-        # slot — per-sequence acceptance would need ragged caches)
+        # slot; per_sequence=True accepts per row)
         agree = (dmat == tmat[:, :-1]).all(dim=0)  # (k,)
         j = int(agree.cumprod(dim=0).sum().item())
 

@@ -251,10 +251,22 @@ class LlamaAttention(nn.Module):
         ops.decode_attn_step / ops.chunk_attn_step for a plain bf16 KVCache,
         ops.decode_attn_mx_step / ops.chunk_attn_mx_step for an MXKVCache.
         Any other cache, and the CPU and odd shapes, take the torch chain
-        below (the reference)."""
+        below (the reference).
+
+        ``pos_t`` with B > 1 elements is one position per sequence (the
+        ragged step): sequence b's tokens sit at pos_t[b] + t and attend its
+        own rows.  It is fused under the same conditions where
+        ops.ragged_attn_enabled().  A sequence with pos_t[b] < 0 or
+        pos_t[b] + S beyond the cache is inactive: its cache rows stay and
+        its attention output is zero on both paths."""
         from ..inference.kv_cache import KVCache, MXKVCache
 
         B, S = q.shape[0], q.shape[1]
+        ragged = B > 1 and pos_t.numel() == B
+        if not ragged and pos_t.numel() != 1:
+            raise ValueError(
+                f"a device-tensor position holds one element, or one per "
+                f"sequence ({B}), got {tuple(pos_t.shape)}")
         rep = self.num_heads_local // self.num_kv_local
         scale = 1.0 / math.sqrt(self.head_dim)
         mx = type(kv_cache) is MXKVCache
@@ -273,6 +285,8 @@ class LlamaAttention(nn.Module):
                 fusable = (ops.chunk_attn_mx_available() if mx
                            else ops.chunk_attn_available())
                 step = ops.chunk_attn_mx_step if mx else ops.chunk_attn_step
+            if ragged:
+                fusable = fusable and ops.ragged_attn_enabled()
         if fusable:
             if S == 1:
                 def _flat(t):
@@ -298,17 +312,43 @@ class LlamaAttention(nn.Module):
                 kf, vf = kf.contiguous(), vf.contiguous()
             bufs = (kv_cache.k, kv_cache.k_scale, kv_cache.v,
                     kv_cache.v_scale) if mx else (kv_cache.k, kv_cache.v)
-            out = step(qf, kf, vf, *bufs, cos, sin, pos_t.reshape(1),
-                       self.num_heads_local, self.num_kv_local, scale)
+            if ragged:
+                out = step(qf, kf, vf, *bufs, cos, sin,
+                           pos_t.reshape(B).contiguous(),
+                           self.num_heads_local, self.num_kv_local, scale,
+                           ragged=True)
+            else:
+                out = step(qf, kf, vf, *bufs, cos, sin, pos_t.reshape(1),
+                           self.num_heads_local, self.num_kv_local, scale)
             if S == 1:
                 out = out.unsqueeze(1)  # (B, 1, H*D)
             if sp:
                 out = out.transpose(0, 1)
             return self.o_proj(out)
         half = self.head_dim // 2
-        tpos = pos_t.reshape(1) + torch.arange(S, device=q.device)  # (S,)
-        c = cos.index_select(0, tpos).view(1, S, 1, half)
-        s = sin.index_select(0, tpos).view(1, S, 1, half)
+        if ragged:
+            if hasattr(kv_cache, "position_index"):
+                raise NotImplementedError(
+                    "per-sequence positions need a plain cache, not a "
+                    "rolling one")
+            Smax = kv_cache.k.shape[2]
+            pos_b = pos_t.reshape(B, 1)
+            active = (pos_b >= 0) & (pos_b + S <= Smax)       # (B, 1)
+            tpos = pos_b + torch.arange(S, device=q.device)   # (B, S)
+            if cos.shape[0] < Smax:
+                raise ValueError(
+                    f"the RoPE table ({cos.shape[0]} rows) must cover the "
+                    f"cache ({Smax} rows)")
+            # an inactive sequence ropes at row 0; its output is zeroed below
+            rows = torch.where(active, tpos, 0).reshape(-1)
+            c = cos.index_select(0, rows).view(B, S, 1, half)
+            s = sin.index_select(0, rows).view(B, S, 1, half)
+            tq = tpos.view(B, 1, 1, S, 1)   # against (B,Hkv,rep,S,Smax)
+        else:
+            tpos = pos_t.reshape(1) + torch.arange(S, device=q.device)  # (S,)
+            c = cos.index_select(0, tpos).view(1, S, 1, half)
+            s = sin.index_select(0, tpos).view(1, S, 1, half)
+            tq = tpos.view(S, 1)
 
         def rope(x):
             x0 = x[..., :half].float()
@@ -333,17 +373,24 @@ class LlamaAttention(nn.Module):
             # rolling window cache (S == 1, its update refuses more): slots
             # carry their GLOBAL position, -1 = unwritten
             idx = kv_cache.position_index().view(1, Smax)
-            invalid = (idx > tpos.view(S, 1)) | (idx < 0)  # (S, Smax)
+            invalid = (idx > tq) | (idx < 0)  # (S, Smax)
         else:
             idx = torch.arange(Smax, device=q.device).view(1, Smax)
-            invalid = idx > tpos.view(S, 1)
+            invalid = idx > tq
         if self.sliding_window is not None:
-            invalid = invalid | (idx <= tpos.view(S, 1) - self.sliding_window)
+            invalid = invalid | (idx <= tq - self.sliding_window)
+        if ragged:
+            # an inactive sequence at a negative position would mask every
+            # row: let it see row 0, its output is zeroed anyway
+            invalid = invalid & ~((idx == 0) & ~active.view(B, 1, 1, 1, 1))
         scores = scores.masked_fill(invalid, float("-inf"))
         probs = torch.softmax(scores, dim=-1).to(q.dtype)
         out = probs.view(B, self.num_kv_local, rep * S, Smax) @ V
         out = out.view(B, self.num_heads_local, S, self.head_dim)
         out = out.transpose(1, 2).reshape(B, S, -1)
+        if ragged:
+            # exact zeros, whatever the stale rows of the sequence hold
+            out = torch.where(active.view(B, 1, 1), out, 0)
         if sp:
             out = out.transpose(0, 1)
         return self.o_proj(out)

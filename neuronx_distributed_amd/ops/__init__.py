@@ -8,6 +8,8 @@ falling back to eager torch.  CPU tensors use plain-torch reference
 implementations (the numerics baseline the GPU kernels are tested against).
 """
 
+import contextlib
+import contextvars
 import ctypes
 import math
 import os
@@ -925,14 +927,55 @@ _DA_SPLIT = 4   # DA_SPLIT of csrc/decode_attn_common.h
 _CA_TMIN, _CA_TMAX = 2, 8   # CA_TMIN / CA_TMAX of csrc/chunk_attn.hip
 
 
+def ragged_attn_available() -> bool:
+    """The per-sequence-position entries of all four fused decode kernels
+    (``ragged=True`` of the ``*_step`` functions below)."""
+    lib = _load()
+    return lib is not None and all(
+        hasattr(lib, n) for n in ("decode_attn_ragged", "decode_attn_mx_ragged",
+                                  "chunk_attn_ragged", "chunk_attn_mx_ragged"))
+
+
+# a context variable: the choice holds for the calling thread (or task) only
+_RAGGED_STEP = contextvars.ContextVar("nxd_ragged_attn_step", default=True)
+
+
+def ragged_attn_enabled() -> bool:
+    """Whether a model should take the ragged entries where it can:
+    :func:`ragged_attn_available`, unless the caller is inside
+    ``ragged_attn_step(False)``."""
+    return _RAGGED_STEP.get() and ragged_attn_available()
+
+
+@contextlib.contextmanager
+def ragged_attn_step(enabled: bool):
+    """Within the block, and for the calling thread only, models with
+    per-sequence positions take the fused ragged step (``enabled``) or their
+    eager chain (not ``enabled``); the ``*_step`` functions themselves are not
+    affected."""
+    token = _RAGGED_STEP.set(bool(enabled))
+    try:
+        yield
+    finally:
+        _RAGGED_STEP.reset(token)
+
+
+def _ragged_entry(lib, name):
+    """The ``_ragged`` sibling of the C entry ``name``."""
+    if not ragged_attn_available():
+        raise RuntimeError(f"nxd_ops library has no {name}_ragged — rebuild")
+    return getattr(lib, name + "_ragged")
+
+
 def _decode_attn_check(who, chunk, q, k, v, cos, sin, pos_t, B, Hq, Hkv, Smax,
-                       dev):
+                       dev, ragged=False):
     """Everything but the cache, for the four fused decode kernels: 2-D
     q2/k2/v2 (one token) or, with ``chunk``, 3-D q3/k3/v3 (T = 2..8 tokens).
     Returns T and the strides to launch with.  One token: the (q, kv) row
     strides, the dense widths when B = 1; 2-byte alignment.  A chunk: the
     element strides (q batch, q token, kv batch, kv token), multiples of 8,
-    and 16-byte pointers."""
+    and 16-byte pointers.  ``pos_t``: one int64, or with ``ragged`` a
+    contiguous (B,) of them."""
     D = _DA_D
     if Hkv < 1 or Hq % Hkv or Hq // Hkv not in (1, 2, 4, 8):
         raise ValueError(f"{who}: Hq={Hq}, Hkv={Hkv} outside the kernel "
@@ -972,7 +1015,14 @@ def _decode_attn_check(who, chunk, q, k, v, cos, sin, pos_t, B, Hq, Hkv, Smax,
             raise ValueError(f"{who}: {name} {tuple(t.shape)} on {t.device} "
                              f"must be (>= {Smax}, {D // 2}) on {dev}: the "
                              f"RoPE table covers the cache")
-    if pos_t.dtype != torch.int64 or pos_t.device != dev \
+    if ragged:
+        if pos_t.dtype != torch.int64 or pos_t.device != dev \
+                or tuple(pos_t.shape) != (B,) or not pos_t.is_contiguous():
+            raise ValueError(f"{who}: a ragged pos_t must be a contiguous "
+                             f"int64 ({B},) tensor on {dev}, got "
+                             f"{pos_t.dtype} {tuple(pos_t.shape)} strides "
+                             f"{pos_t.stride()} on {pos_t.device}")
+    elif pos_t.dtype != torch.int64 or pos_t.device != dev \
             or pos_t.numel() != 1:
         raise ValueError(f"{who}: pos_t must be one int64 on {dev}, got "
                          f"{pos_t.dtype} {tuple(pos_t.shape)} on "
@@ -1038,11 +1088,19 @@ def decode_attn_step(q2: torch.Tensor, k2: torch.Tensor, v2: torch.Tensor,
                      kcache: torch.Tensor, vcache: torch.Tensor,
                      cos: torch.Tensor, sin: torch.Tensor,
                      pos_t: torch.Tensor, Hq: int, Hkv: int,
-                     scale: float) -> torch.Tensor:
+                     scale: float, *, ragged: bool = False) -> torch.Tensor:
     """One fused decode-attention step: RoPE(q,k) + cache append at the
     device position ``pos_t`` + flash-decode over the cache + GQA.
     q2 (B, Hq*128), k2/v2 (B, Hkv*128) bf16 pre-rope; kcache/vcache
     (B, Hkv, Smax, 128); cos/sin (>= Smax, 64) fp32 -> out (B, Hq*128).
+
+    ``ragged``: ``pos_t`` is a contiguous int64 (B,) tensor, one position
+    per sequence.  Sequence b appends at row ``pos_t[b]`` and attends its own
+    rows [0, pos_t[b]]; its result is what the call gives for that sequence
+    alone.  A sequence with a position outside [0, Smax) is inactive: its
+    cache is left alone and its output row is zero.  (All four ``*_step``
+    functions take the flag; a chunk of T tokens is inactive unless
+    ``0 <= pos_t[b]`` and ``pos_t[b] + T <= Smax``.)
 
     q2/k2/v2 may be row-strided views (e.g. slices of one fused-QKV GEMM
     output): only the last dim must be dense (stride 1).  A wrong dtype or
@@ -1053,9 +1111,10 @@ def decode_attn_step(q2: torch.Tensor, k2: torch.Tensor, v2: torch.Tensor,
         raise RuntimeError("nxd_ops library has no decode_attn — rebuild")
     B, Smax = _decode_attn_check_cache(who, kcache, vcache, Hkv)
     T, st = _decode_attn_check(who, False, q2, k2, v2, cos, sin, pos_t, B, Hq,
-                               Hkv, Smax, kcache.device)
+                               Hkv, Smax, kcache.device, ragged)
+    fn = _ragged_entry(lib, "decode_attn") if ragged else lib.decode_attn
     return _decode_attn_launch(
-        lib.decode_attn, False, (q2, k2, v2, kcache, vcache, cos, sin, pos_t),
+        fn, False, (q2, k2, v2, kcache, vcache, cos, sin, pos_t),
         B, T, Hq, Hkv, Smax, scale, st)
 
 
@@ -1378,7 +1437,8 @@ def decode_attn_mx_step(q2: torch.Tensor, k2: torch.Tensor, v2: torch.Tensor,
                         v_payload: torch.Tensor, v_scale: torch.Tensor,
                         cos: torch.Tensor, sin: torch.Tensor,
                         pos_t: torch.Tensor, Hq: int, Hkv: int,
-                        scale: float) -> torch.Tensor:
+                        scale: float, *, ragged: bool = False
+                        ) -> torch.Tensor:
     """:func:`decode_attn_step` over an MXFP8 cache (``MXKVCache`` buffers:
     e4m3 payload (B, Hkv, Smax, 128) + e8m0 scales (B, Hkv, Smax, 4), both
     uint8).  The new K (after RoPE) and V rows are quantized and appended at
@@ -1397,10 +1457,11 @@ def decode_attn_mx_step(q2: torch.Tensor, k2: torch.Tensor, v2: torch.Tensor,
         raise ValueError(f"{who}: cache {tuple(k_payload.shape)} with "
                          f"Hkv={Hkv} outside the kernel contract (D = 128)")
     T, st = _decode_attn_check(who, False, q2, k2, v2, cos, sin, pos_t, B, Hq,
-                               Hkv, Smax, dev)
+                               Hkv, Smax, dev, ragged)
+    fn = _ragged_entry(lib, "decode_attn_mx") if ragged else lib.decode_attn_mx
     return _decode_attn_launch(
-        lib.decode_attn_mx, False, (q2, k2, v2, k_payload, k_scale, v_payload,
-                                    v_scale, cos, sin, pos_t),
+        fn, False, (q2, k2, v2, k_payload, k_scale, v_payload, v_scale, cos,
+                    sin, pos_t),
         B, T, Hq, Hkv, Smax, scale, st)
 
 
@@ -1470,12 +1531,13 @@ def chunk_attn_step(q3: torch.Tensor, k3: torch.Tensor, v3: torch.Tensor,
                     kcache: torch.Tensor, vcache: torch.Tensor,
                     cos: torch.Tensor, sin: torch.Tensor,
                     pos_t: torch.Tensor, Hq: int, Hkv: int,
-                    scale: float) -> torch.Tensor:
+                    scale: float, *, ragged: bool = False) -> torch.Tensor:
     """The multi-token sibling of :func:`decode_attn_step`: T = 2..8 new
     tokens per sequence.  q3 (B, T, Hq*128), k3/v3 (B, T, Hkv*128) bf16
     pre-rope (row-strided views with a dense last dim are fine);
     kcache/vcache bf16 (B, Hkv, Smax, 128); cos/sin (>= Smax, 64) fp32;
-    ``pos_t`` one device int64 -> out (B, T, Hq*128).
+    ``pos_t`` one device int64 (``ragged``: (B,) of them, see
+    :func:`decode_attn_step`) -> out (B, T, Hq*128).
 
     Token t is roped at position pos + t, its K/V row is stored at cache row
     pos + t (rows at or beyond Smax are not written) and it attends cache
@@ -1488,9 +1550,10 @@ def chunk_attn_step(q3: torch.Tensor, k3: torch.Tensor, v3: torch.Tensor,
         raise RuntimeError("nxd_ops library has no chunk_attn — rebuild")
     B, Smax = _decode_attn_check_cache(who, kcache, vcache, Hkv)
     T, st = _decode_attn_check(who, True, q3, k3, v3, cos, sin, pos_t, B, Hq,
-                               Hkv, Smax, kcache.device)
+                               Hkv, Smax, kcache.device, ragged)
+    fn = _ragged_entry(lib, "chunk_attn") if ragged else lib.chunk_attn
     return _decode_attn_launch(
-        lib.chunk_attn, True, (q3, k3, v3, kcache, vcache, cos, sin, pos_t),
+        fn, True, (q3, k3, v3, kcache, vcache, cos, sin, pos_t),
         B, T, Hq, Hkv, Smax, scale, st)
 
 
@@ -1499,7 +1562,8 @@ def chunk_attn_mx_step(q3: torch.Tensor, k3: torch.Tensor, v3: torch.Tensor,
                        v_payload: torch.Tensor, v_scale: torch.Tensor,
                        cos: torch.Tensor, sin: torch.Tensor,
                        pos_t: torch.Tensor, Hq: int, Hkv: int,
-                       scale: float) -> torch.Tensor:
+                       scale: float, *, ragged: bool = False
+                       ) -> torch.Tensor:
     """:func:`chunk_attn_step` over an MXFP8 cache (``MXKVCache`` buffers).
     The T new K (after RoPE) and V rows are stored as
     ``pack_mx(quantize_mx(row))`` and the output attends to the cache as
@@ -1516,8 +1580,9 @@ def chunk_attn_mx_step(q3: torch.Tensor, k3: torch.Tensor, v3: torch.Tensor,
                          f"with Hkv={Hkv} outside the kernel contract "
                          f"(D = 128, GPU)")
     T, st = _decode_attn_check(who, True, q3, k3, v3, cos, sin, pos_t, B, Hq,
-                               Hkv, Smax, dev)
+                               Hkv, Smax, dev, ragged)
+    fn = _ragged_entry(lib, "chunk_attn_mx") if ragged else lib.chunk_attn_mx
     return _decode_attn_launch(
-        lib.chunk_attn_mx, True, (q3, k3, v3, k_payload, k_scale, v_payload,
-                                  v_scale, cos, sin, pos_t),
+        fn, True, (q3, k3, v3, k_payload, k_scale, v_payload, v_scale, cos,
+                   sin, pos_t),
         B, T, Hq, Hkv, Smax, scale, st)

@@ -2,6 +2,10 @@
 // tokens against a KV cache that already holds rows, from a device position.
 // The multi-token sibling of decode_attn.hip / decode_attn_mx.hip, for the
 // verify forward of speculative decoding and for chunked prefill.
+// chunk_attn / chunk_attn_mx take one device position for the batch;
+// chunk_attn_ragged / chunk_attn_mx_ragged take one per sequence (RAGGED of
+// decode_attn_common.h: an inactive sequence, one whose T rows do not all fit
+// the cache, gets no append, a neutral partial and zeros out).
 //
 //   chunk_attn    : bf16 cache (B, Hkv, Smax, 128)
 //   chunk_attn_mx : MXFP8 cache (MXKVCache: e4m3 payload (B, Hkv, Smax, 128)
@@ -60,9 +64,9 @@
 //
 // Layouts: q (B, T, Hq*128), k/v (B, T, Hkv*128) bf16 pre-RoPE with element
 // strides (batch, token) and a dense last dim; cos/sin (>= Smax, 64) fp32;
-// pos_ptr one device int64; workspace part_o (B*Hkv*DA_SPLIT, R, 128) fp32,
-// part_ml (..., R, 2) = (m, l) in the exp2 domain, m = -1e30 for a split
-// without rows, as in decode_attn_common.h.
+// pos_ptr one device int64 (RAGGED: B of them); workspace part_o
+// (B*Hkv*DA_SPLIT, R, 128) fp32, part_ml (..., R, 2) = (m, l) in the exp2
+// domain, m = -1e30 for a split without rows, as in decode_attn_common.h.
 
 #include "decode_attn_common.h"
 #include "flash_common.h"
@@ -78,8 +82,9 @@
 
 // the device position, clamped to [-CA_TMAX, Smax]: outside that range no
 // row is written and the set of rows attended does not change any more
-__device__ __forceinline__ int ca_pos(const long* pos_ptr, int Smax) {
-  const long p = *pos_ptr;
+template <bool RAGGED>
+__device__ __forceinline__ int ca_pos(const long* pos_ptr, int b, int Smax) {
+  const long p = da_pos<RAGGED>(pos_ptr, b);
   return (int)max(min(p, (long)Smax), -(long)CA_TMAX);
 }
 
@@ -94,7 +99,7 @@ __device__ __forceinline__ void ca_wave_sync() {
 // ---------------------------------------------------------------------------
 // 1. append: block (b, kvh, t), 128 threads
 // ---------------------------------------------------------------------------
-template <bool MX>
+template <bool MX, bool RAGGED>
 __global__ void __launch_bounds__(128)
 chunk_attn_append(const short* __restrict__ kin, const short* __restrict__ vin,
                   void* __restrict__ kc, uint8_t* __restrict__ ksc,
@@ -108,7 +113,8 @@ chunk_attn_append(const short* __restrict__ kin, const short* __restrict__ vin,
   const int kvh = pair % Hkv;
   const int b = pair / Hkv;
   const int tid = threadIdx.x;
-  const int row = ca_pos(pos_ptr, Smax) + tok;
+  if (RAGGED && !da_active(da_pos<RAGGED>(pos_ptr, b), T, Smax)) return;
+  const int row = ca_pos<RAGGED>(pos_ptr, b, Smax) + tok;
   if (row < 0 || row >= Smax) return;  // the whole block
   const long src = (long)b * kv_bs + (long)tok * kv_ts + kvh * DA_D;
   const long dst = ((long)pair * Smax + row);
@@ -262,7 +268,7 @@ __device__ __forceinline__ void ca_rope8(uint4v xlo, uint4v xhi,
 // Second launch bound: HIP's minimum waves per SIMD.  With one query block
 // two workgroups share a CU (2 x 64 KB of LDS, 256 registers per lane); two
 // query blocks need more registers than that and run one workgroup per CU.
-template <int REP, int NQB, bool MX>
+template <int REP, int NQB, bool MX, bool RAGGED>
 __global__ void __launch_bounds__(DA_WAVES * 64, NQB == 1 ? 2 : 1)
 chunk_attn_part(const short* __restrict__ qin, const void* __restrict__ kc,
                 const uint8_t* __restrict__ ksc, const void* __restrict__ vc,
@@ -285,7 +291,12 @@ chunk_attn_part(const short* __restrict__ qin, const void* __restrict__ kc,
   const int hi = lane >> 5;
   const int R = REP * T;
 
-  const int pos = __builtin_amdgcn_readfirstlane(ca_pos(pos_ptr, Smax));
+  if (RAGGED && !da_active(da_pos<RAGGED>(pos_ptr, b), T, Smax)) {
+    da_store_neutral(wg, R, DA_WAVES * 64, part_o, part_ml);
+    return;  // the whole workgroup, before any barrier
+  }
+  const int pos =
+      __builtin_amdgcn_readfirstlane(ca_pos<RAGGED>(pos_ptr, b, Smax));
   const int n = max(min(pos + T, Smax), 0);  // rows [0, n) exist
   const int ntiles = (n + CA_TILE - 1) / CA_TILE;
   const int tchunk = (ntiles + DA_SPLIT - 1) / DA_SPLIT;
@@ -491,7 +502,7 @@ static bool ca_launch_ok(const void* q, const void* k, const void* v,
   return (long)B * Hkv * T <= 0x7FFFFFFFL && (long)Smax + T < 0x7FFFFFFFL;
 }
 
-template <bool MX>
+template <bool MX, bool RAGGED>
 static int ca_launch(const void* q, const void* k, const void* v, void* kc,
                      void* ksc, void* vc, void* vsc, const void* cosp,
                      const void* sinp, const void* pos_ptr, void* part_o,
@@ -504,15 +515,16 @@ static int ca_launch(const void* q, const void* k, const void* v, void* kc,
   if (((uintptr_t)kc | (uintptr_t)vc) % 16 ||
       (MX && ((uintptr_t)ksc | (uintptr_t)vsc) % 4))
     return 1;
-  chunk_attn_append<MX><<<B * Hkv * T, 128, 0, stream>>>(
+  chunk_attn_append<MX, RAGGED><<<B * Hkv * T, 128, 0, stream>>>(
       (const short*)k, (const short*)v, kc, (uint8_t*)ksc, vc, (uint8_t*)vsc,
       (const float*)cosp, (const float*)sinp, (const long*)pos_ptr, T, Hkv,
       Smax, kv_bs, kv_ts);
   da_for_rep(Hq / Hkv, [&](auto rep) {
     constexpr int R = decltype(rep)::value;
-    auto part = chunk_attn_part<R, 1, MX>;  // two query blocks: rep 8 only
+    // two query blocks: rep 8 only
+    auto part = chunk_attn_part<R, 1, MX, RAGGED>;
     if constexpr (R == 8)
-      if (R * T > 32) part = chunk_attn_part<R, 2, MX>;
+      if (R * T > 32) part = chunk_attn_part<R, 2, MX, RAGGED>;
     part<<<B * Hkv * DA_SPLIT, DA_WAVES * 64, 0, stream>>>(
         (const short*)q, kc, (const uint8_t*)ksc, vc, (const uint8_t*)vsc,
         (const float*)cosp, (const float*)sinp, (const long*)pos_ptr,
@@ -530,9 +542,10 @@ extern "C" int chunk_attn(const void* q, const void* k, const void* v,
                           void* part_ml, void* outp, int B, int T, int Hq,
                           int Hkv, int Smax, float scale, long q_bs, long q_ts,
                           long kv_bs, long kv_ts, hipStream_t stream) {
-  return ca_launch<false>(q, k, v, kcache, nullptr, vcache, nullptr, cosp,
-                          sinp, pos_ptr, part_o, part_ml, outp, B, T, Hq, Hkv,
-                          Smax, scale, q_bs, q_ts, kv_bs, kv_ts, stream);
+  return ca_launch<false, false>(q, k, v, kcache, nullptr, vcache, nullptr,
+                                 cosp, sinp, pos_ptr, part_o, part_ml, outp, B,
+                                 T, Hq, Hkv, Smax, scale, q_bs, q_ts, kv_bs,
+                                 kv_ts, stream);
 }
 
 extern "C" int chunk_attn_mx(const void* q, const void* k, const void* v,
@@ -542,7 +555,35 @@ extern "C" int chunk_attn_mx(const void* q, const void* k, const void* v,
                              void* outp, int B, int T, int Hq, int Hkv,
                              int Smax, float scale, long q_bs, long q_ts,
                              long kv_bs, long kv_ts, hipStream_t stream) {
-  return ca_launch<true>(q, k, v, kpay, ksc, vpay, vsc, cosp, sinp, pos_ptr,
-                         part_o, part_ml, outp, B, T, Hq, Hkv, Smax, scale,
-                         q_bs, q_ts, kv_bs, kv_ts, stream);
+  return ca_launch<true, false>(q, k, v, kpay, ksc, vpay, vsc, cosp, sinp,
+                                pos_ptr, part_o, part_ml, outp, B, T, Hq, Hkv,
+                                Smax, scale, q_bs, q_ts, kv_bs, kv_ts, stream);
+}
+
+// The same two with pos_ptr B device int64, one per sequence.
+extern "C" int chunk_attn_ragged(const void* q, const void* k, const void* v,
+                                 void* kcache, void* vcache, const void* cosp,
+                                 const void* sinp, const void* pos_ptr,
+                                 void* part_o, void* part_ml, void* outp,
+                                 int B, int T, int Hq, int Hkv, int Smax,
+                                 float scale, long q_bs, long q_ts, long kv_bs,
+                                 long kv_ts, hipStream_t stream) {
+  return ca_launch<false, true>(q, k, v, kcache, nullptr, vcache, nullptr,
+                                cosp, sinp, pos_ptr, part_o, part_ml, outp, B,
+                                T, Hq, Hkv, Smax, scale, q_bs, q_ts, kv_bs,
+                                kv_ts, stream);
+}
+
+extern "C" int chunk_attn_mx_ragged(const void* q, const void* k,
+                                    const void* v, void* kpay, void* ksc,
+                                    void* vpay, void* vsc, const void* cosp,
+                                    const void* sinp, const void* pos_ptr,
+                                    void* part_o, void* part_ml, void* outp,
+                                    int B, int T, int Hq, int Hkv, int Smax,
+                                    float scale, long q_bs, long q_ts,
+                                    long kv_bs, long kv_ts,
+                                    hipStream_t stream) {
+  return ca_launch<true, true>(q, k, v, kpay, ksc, vpay, vsc, cosp, sinp,
+                               pos_ptr, part_o, part_ml, outp, B, T, Hq, Hkv,
+                               Smax, scale, q_bs, q_ts, kv_bs, kv_ts, stream);
 }

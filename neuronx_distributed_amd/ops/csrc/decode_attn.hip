@@ -23,11 +23,14 @@
 // Constants, layouts and every phase-1 piece but the walk over the cache
 // are in decode_attn_common.h, shared with decode_attn_mx.hip.
 // kcache/vcache are bf16 (B, Hkv, Smax, D).
+//
+// decode_attn takes one device position for the batch; decode_attn_ragged
+// takes one per sequence (decode_attn_common.h, RAGGED).
 
 #include "decode_attn_common.h"
 #include "mfma.h"
 
-template <int REP>
+template <int REP, bool RAGGED>
 __global__ void __launch_bounds__(DA_WAVES * 64)
 decode_attn_part(const short* __restrict__ qlin,
                     const short* __restrict__ klin,
@@ -40,7 +43,11 @@ decode_attn_part(const short* __restrict__ qlin,
                     int B, int Hq, int Hkv, int Smax, float scale,
                     int qstride, int kvstride) {
   DaCoord c;
-  da_coord<REP>(c, pos_ptr, Hkv);
+  da_coord<REP, RAGGED>(c, pos_ptr, Hkv);
+  if (RAGGED && !da_active(c.pos, 1, Smax)) {  // the whole workgroup
+    da_store_neutral(c.wg, REP, DA_WAVES * 64, part_o, part_ml);
+    return;
+  }
   const int tid = c.tid, hl = c.hl;
 
   __shared__ float qr[REP][DA_D];
@@ -183,17 +190,16 @@ extern "C" int decode_attn_merge_launch(const void* part_o,
   });
 }
 
-// Returns non-zero, launching nothing, outside da_launch_ok's contract.
-extern "C" int decode_attn(const void* qlin, const void* klin,
-                           const void* vlin, void* kcache, void* vcache,
-                           const void* cosp, const void* sinp,
-                           const void* pos_ptr, void* part_o, void* part_ml,
-                           void* outp, int B, int Hq, int Hkv, int Smax,
-                           float scale, int qstride, int kvstride,
-                           hipStream_t stream) {
+template <bool RAGGED>
+static int da_launch(const void* qlin, const void* klin, const void* vlin,
+                     void* kcache, void* vcache, const void* cosp,
+                     const void* sinp, const void* pos_ptr, void* part_o,
+                     void* part_ml, void* outp, int B, int Hq, int Hkv,
+                     int Smax, float scale, int qstride, int kvstride,
+                     hipStream_t stream) {
   if (!da_launch_ok(B, Hq, Hkv, Smax, qstride, kvstride)) return 1;
   da_for_rep(Hq / Hkv, [&](auto rep) {
-    decode_attn_part<decltype(rep)::value>
+    decode_attn_part<decltype(rep)::value, RAGGED>
         <<<B * Hkv * DA_SPLIT, DA_WAVES * 64, 0, stream>>>(
             (const short*)qlin, (const short*)klin, (const short*)vlin,
             (short*)kcache, (short*)vcache, (const float*)cosp,
@@ -202,4 +208,31 @@ extern "C" int decode_attn(const void* qlin, const void* klin,
   });
   return decode_attn_merge_launch(part_o, part_ml, outp, B, 1, Hq, Hkv,
                                   stream);
+}
+
+// Both return non-zero, launching nothing, outside da_launch_ok's contract.
+// decode_attn: pos_ptr one int64.  decode_attn_ragged: B of them.
+extern "C" int decode_attn(const void* qlin, const void* klin,
+                           const void* vlin, void* kcache, void* vcache,
+                           const void* cosp, const void* sinp,
+                           const void* pos_ptr, void* part_o, void* part_ml,
+                           void* outp, int B, int Hq, int Hkv, int Smax,
+                           float scale, int qstride, int kvstride,
+                           hipStream_t stream) {
+  return da_launch<false>(qlin, klin, vlin, kcache, vcache, cosp, sinp,
+                          pos_ptr, part_o, part_ml, outp, B, Hq, Hkv, Smax,
+                          scale, qstride, kvstride, stream);
+}
+
+extern "C" int decode_attn_ragged(const void* qlin, const void* klin,
+                                  const void* vlin, void* kcache,
+                                  void* vcache, const void* cosp,
+                                  const void* sinp, const void* pos_ptr,
+                                  void* part_o, void* part_ml, void* outp,
+                                  int B, int Hq, int Hkv, int Smax,
+                                  float scale, int qstride, int kvstride,
+                                  hipStream_t stream) {
+  return da_launch<true>(qlin, klin, vlin, kcache, vcache, cosp, sinp,
+                         pos_ptr, part_o, part_ml, outp, B, Hq, Hkv, Smax,
+                         scale, qstride, kvstride, stream);
 }

@@ -12,9 +12,17 @@
 // Layouts (bf16 unless noted): q_lin (B, Hq*D) row-stride qstride,
 // k_lin/v_lin (B, Hkv*D) row-stride kvstride (strided fused-QKV views feed
 // directly); cos/sin (>= Smax, D/2) fp32; pos_ptr device int64
-// (hipGraph-replayable); workspace part_o (B*Hkv*DA_SPLIT, REP, D) fp32 +
-// part_ml (..., 2) fp32 holding (m, l) in the exp2 domain, m = -1e30 for a
-// split without rows.  D = 128.  No atomics.
+// (hipGraph-replayable): one for the whole batch, or with RAGGED one per
+// sequence (B of them, dense); workspace part_o (B*Hkv*DA_SPLIT, REP, D)
+// fp32 + part_ml (..., 2) fp32 holding (m, l) in the exp2 domain, m = -1e30
+// for a split without rows.  D = 128.  No atomics.
+//
+// RAGGED (the *_ragged entries): sequence b appends at pos_ptr[b] and attends
+// its own rows only.  A workgroup serves one b, so its position stays
+// workgroup-uniform.  A sequence whose new rows do not all lie in [0, Smax)
+// is INACTIVE: its workgroups touch neither the cache nor the RoPE table,
+// store the neutral partial (m = -1e30, l = 0, o = 0) and leave before the
+// first barrier, and phase 2 writes zeros for it.
 #pragma once
 
 #include <type_traits>
@@ -70,7 +78,32 @@ struct DaCoord {
   long pos, r0, r1;        // append position; this split's rows [r0, r1)
 };
 
-template <int REP>
+// pos_ptr[b * pos_stride], the stride a compile-time 0 (one position) or 1
+template <bool RAGGED>
+__device__ __forceinline__ long da_pos(const long* pos_ptr, int b) {
+  return RAGGED ? pos_ptr[b] : *pos_ptr;
+}
+
+// a RAGGED sequence takes part only with all T new rows inside the cache
+__device__ __forceinline__ bool da_active(long pos, int T, int Smax) {
+  return pos >= 0 && pos + T <= (long)Smax;
+}
+
+// The neutral partial of an inactive sequence's workgroup: R workspace rows
+// of zeros with (m, l) = (-1e30, 0).  The whole workgroup calls it.
+__device__ __forceinline__ void da_store_neutral(int wg, int R, int nthreads,
+                                                 float* part_o,
+                                                 float* part_ml) {
+  const int tid = threadIdx.x;
+  for (int i = tid; i < R * DA_D; i += nthreads)
+    part_o[(long)wg * R * DA_D + i] = 0.f;
+  for (int i = tid; i < R; i += nthreads) {
+    part_ml[((long)wg * R + i) * 2 + 0] = DA_NEG;
+    part_ml[((long)wg * R + i) * 2 + 1] = 0.f;
+  }
+}
+
+template <int REP, bool RAGGED = false>
 __device__ __forceinline__ void da_coord(DaCoord& c, const long* pos_ptr,
                                             int Hkv) {
   c.wg = blockIdx.x;
@@ -84,7 +117,7 @@ __device__ __forceinline__ void da_coord(DaCoord& c, const long* pos_ptr,
   c.quarter = c.lane >> 4;
   c.hl = c.lane & 15;
   c.wid = __builtin_amdgcn_readfirstlane(c.tid >> 6);
-  c.pos = *pos_ptr;
+  c.pos = da_pos<RAGGED>(pos_ptr, c.b);
   const long chunk = (c.pos + DA_SPLIT - 1) / DA_SPLIT;
   c.r0 = (long)c.s * chunk;
   c.r1 = min(c.pos, c.r0 + chunk);

@@ -33,6 +33,9 @@
 // Constants, the layouts of q/k/v, the RoPE tables and the workspace, and
 // every phase-1 piece but the walk over the cache and the append are in
 // decode_attn_common.h, shared with decode_attn.hip.
+//
+// decode_attn_mx takes one device position for the batch;
+// decode_attn_mx_ragged takes one per sequence (decode_attn_common.h, RAGGED).
 
 #include "decode_attn_common.h"
 #include "mfma.h"
@@ -71,7 +74,7 @@ __device__ __forceinline__ void damx_append_block(
   scales[blk] = (uint8_t)(e + 127);
 }
 
-template <int REP>
+template <int REP, bool RAGGED>
 __global__ void __launch_bounds__(DA_WAVES * 64)
 decode_attn_mx_part(const short* __restrict__ qlin,
                     const short* __restrict__ klin,
@@ -85,7 +88,11 @@ decode_attn_mx_part(const short* __restrict__ qlin,
                     int B, int Hq, int Hkv, int Smax, float scale,
                     int qstride, int kvstride) {
   DaCoord c;
-  da_coord<REP>(c, pos_ptr, Hkv);
+  da_coord<REP, RAGGED>(c, pos_ptr, Hkv);
+  if (RAGGED && !da_active(c.pos, 1, Smax)) {  // the whole workgroup
+    da_store_neutral(c.wg, REP, DA_WAVES * 64, part_o, part_ml);
+    return;
+  }
   const int tid = c.tid, quarter = c.quarter, hl = c.hl;
   const int blk = hl >> 2;           // the 32-block the lane's dims lie in
   const long r1 = c.r1;
@@ -222,17 +229,17 @@ decode_attn_mx_part(const short* __restrict__ qlin,
   da_merge_store<REP>(c, merge_o, merge_ml, part_o, part_ml);
 }
 
-// Returns non-zero, launching nothing, outside da_launch_ok's contract.
-extern "C" int decode_attn_mx(const void* qlin, const void* klin,
-                              const void* vlin, void* kpay, void* ksc,
-                              void* vpay, void* vsc, const void* cosp,
-                              const void* sinp, const void* pos_ptr,
-                              void* part_o, void* part_ml, void* outp, int B,
-                              int Hq, int Hkv, int Smax, float scale,
-                              int qstride, int kvstride, hipStream_t stream) {
+template <bool RAGGED>
+static int damx_launch(const void* qlin, const void* klin, const void* vlin,
+                       void* kpay, void* ksc, void* vpay, void* vsc,
+                       const void* cosp, const void* sinp,
+                       const void* pos_ptr, void* part_o, void* part_ml,
+                       void* outp, int B, int Hq, int Hkv, int Smax,
+                       float scale, int qstride, int kvstride,
+                       hipStream_t stream) {
   if (!da_launch_ok(B, Hq, Hkv, Smax, qstride, kvstride)) return 1;
   da_for_rep(Hq / Hkv, [&](auto rep) {
-    decode_attn_mx_part<decltype(rep)::value>
+    decode_attn_mx_part<decltype(rep)::value, RAGGED>
         <<<B * Hkv * DA_SPLIT, DA_WAVES * 64, 0, stream>>>(
             (const short*)qlin, (const short*)klin, (const short*)vlin,
             (uint8_t*)kpay, (uint8_t*)ksc, (uint8_t*)vpay, (uint8_t*)vsc,
@@ -242,6 +249,33 @@ extern "C" int decode_attn_mx(const void* qlin, const void* klin,
   });
   return decode_attn_merge_launch(part_o, part_ml, outp, B, 1, Hq, Hkv,
                                   stream);
+}
+
+// Both return non-zero, launching nothing, outside da_launch_ok's contract.
+// decode_attn_mx: pos_ptr one int64.  decode_attn_mx_ragged: B of them.
+extern "C" int decode_attn_mx(const void* qlin, const void* klin,
+                              const void* vlin, void* kpay, void* ksc,
+                              void* vpay, void* vsc, const void* cosp,
+                              const void* sinp, const void* pos_ptr,
+                              void* part_o, void* part_ml, void* outp, int B,
+                              int Hq, int Hkv, int Smax, float scale,
+                              int qstride, int kvstride, hipStream_t stream) {
+  return damx_launch<false>(qlin, klin, vlin, kpay, ksc, vpay, vsc, cosp,
+                            sinp, pos_ptr, part_o, part_ml, outp, B, Hq, Hkv,
+                            Smax, scale, qstride, kvstride, stream);
+}
+
+extern "C" int decode_attn_mx_ragged(const void* qlin, const void* klin,
+                                     const void* vlin, void* kpay, void* ksc,
+                                     void* vpay, void* vsc, const void* cosp,
+                                     const void* sinp, const void* pos_ptr,
+                                     void* part_o, void* part_ml, void* outp,
+                                     int B, int Hq, int Hkv, int Smax,
+                                     float scale, int qstride, int kvstride,
+                                     hipStream_t stream) {
+  return damx_launch<true>(qlin, klin, vlin, kpay, ksc, vpay, vsc, cosp,
+                           sinp, pos_ptr, part_o, part_ml, outp, B, Hq, Hkv,
+                           Smax, scale, qstride, kvstride, stream);
 }
 
 // ---------------------------------------------------------------------------
