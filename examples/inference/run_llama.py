@@ -32,8 +32,10 @@ def main():
     p.add_argument("--prompt-len", type=int, default=512)
     p.add_argument("--new-tokens", type=int, default=128)
     p.add_argument("--top-k", type=int, default=0, help="0 = greedy")
-    p.add_argument("--kv-format", default="bf16", choices=["bf16", "mxfp8"],
-                   help="KV-cache storage: the model dtype or MXFP8")
+    p.add_argument("--kv-format", default="bf16",
+                   choices=["bf16", "mxfp8", "paged"],
+                   help="KV-cache storage: the model dtype, MXFP8, or the "
+                        "model dtype in a page pool")
     args = p.parse_args()
 
     os.environ.setdefault("MASTER_ADDR", "127.0.0.1")

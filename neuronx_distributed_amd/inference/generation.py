@@ -7,7 +7,7 @@ from typing import Optional
 import torch
 
 from ..utils.sampling import Sampler
-from .kv_cache import build_kv_caches
+from .kv_cache import PAGE_ROWS, PagePool, build_kv_caches
 
 
 def check_prompt_lens(prompt_lens, input_ids: torch.Tensor) -> torch.Tensor:
@@ -36,9 +36,19 @@ def ragged_output(input_ids: torch.Tensor, lens: torch.Tensor,
 
 def _generate_ragged(model, input_ids, prompt_lens, max_new_tokens, sampler,
                      eos_token_id, use_cuda_graph, kv_format, pad_token_id,
-                     n_kv_local, model_dtype):
+                     n_kv_local, model_dtype, who="prompt_lens"):
     """generate() for right-padded prompts of different lengths: one padded
-    prefill, then decode with one position per sequence."""
+    prefill, then decode with one position per sequence.
+
+    ``kv_format="paged"``: one PagePool of sum_b ceil((len_b +
+    max_new_tokens) / 16) pages, every sequence allocated up front, so the
+    table is static while the decode graph replays; the prefill drops the
+    padding rows beyond a sequence's pages.  The cache of a sequence then
+    ends on a page boundary: the model's RoPE table must cover
+    16 * ceil((len_b + max_new_tokens) / 16) rows, up to 15 more than the
+    tokens need.
+
+    ``who``: the argument the caller chose this path with, for messages."""
     from .decode_graph import GraphDecoder
 
     cfg = model.config
@@ -46,20 +56,27 @@ def _generate_ragged(model, input_ids, prompt_lens, max_new_tokens, sampler,
     dev = input_ids.device
     lens = check_prompt_lens(prompt_lens, input_ids)
     if max_new_tokens < 1:
-        raise ValueError(f"prompt_lens: max_new_tokens {max_new_tokens} must "
+        raise ValueError(f"{who}: max_new_tokens {max_new_tokens} must "
                          f"be at least 1")
     window = getattr(cfg, "sliding_window", None)
     if window is not None and window < S + max_new_tokens:
         raise NotImplementedError(
-            "prompt_lens with a sliding window smaller than the sequence: "
-            "the rolling cache keeps one position for the whole batch")
+            f"{who} with a sliding window smaller than the sequence: "
+            f"the rolling cache keeps one position for the whole batch")
     if not getattr(model, "supports_tensor_position", False):
         raise NotImplementedError(
-            "prompt_lens needs a model that takes device-tensor positions")
+            f"{who} needs a model that takes device-tensor positions")
+    pool = None
+    if kv_format == "paged":
+        rows = [n + max_new_tokens for n in lens.tolist()]
+        pages = [-(-n // PAGE_ROWS) for n in rows]
+        pool = PagePool(sum(pages), B, max(pages), dev)
+        for b, n in enumerate(rows):
+            pool.allocate(b, n)
     caches = build_kv_caches(cfg.num_hidden_layers, B, n_kv_local,
                              S + max_new_tokens, cfg.head_dim,
                              dtype=model_dtype, device=dev,
-                             kv_format=kv_format)
+                             kv_format=kv_format, page_pool=pool)
     # padding sits to the right: no real token attends it, and the cache rows
     # it leaves at >= len_b are masked until a decode step overwrites them
     logits = model(input_ids, kv_caches=caches, pos_offset=0)
@@ -102,7 +119,10 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int = 32,
     On GPU the per-token decode step is captured in a hipGraph and
     replayed (launch-bound otherwise); pass ``use_cuda_graph=False`` for
     the eager loop.  ``kv_format="mxfp8"`` keeps the KV cache in MXFP8
-    (inference.kv_cache.MXKVCache) instead of the model dtype."""
+    (inference.kv_cache.MXKVCache) instead of the model dtype;
+    ``kv_format="paged"`` keeps it in a page pool sized for the sequences'
+    own lengths (inference.kv_cache.PagedKVCache) and always returns the
+    ``prompt_lens`` layout (without ``prompt_lens``, every length is S)."""
     from ..parallel import parallel_state as ps
     from .decode_graph import GraphDecoder
 
@@ -113,11 +133,14 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int = 32,
     kv_mult = max(1, tp // cfg.num_key_value_heads)
     n_kv_local = cfg.num_key_value_heads * kv_mult // tp
     model_dtype = next(model.parameters()).dtype
-    if prompt_lens is not None:
+    if prompt_lens is not None or kv_format == "paged":
+        who = "prompt_lens"
+        if prompt_lens is None:   # a paged cache has one position per sequence
+            prompt_lens, who = [S] * B, "kv_format='paged'"
         return _generate_ragged(model, input_ids, prompt_lens,
                                 max_new_tokens, sampler, eos_token_id,
                                 use_cuda_graph, kv_format, pad_token_id,
-                                n_kv_local, model_dtype)
+                                n_kv_local, model_dtype, who)
     caches = build_kv_caches(cfg.num_hidden_layers, B, n_kv_local,
                              S + max_new_tokens, cfg.head_dim,
                              dtype=model_dtype, device=input_ids.device,

@@ -77,12 +77,12 @@ def _ragged_write(pos: torch.Tensor, *pairs) -> None:
         buf.scatter_(2, idx, torch.where(active, new, buf.gather(2, idx)))
 
 
-KV_FORMATS = (None, "mxfp8")
+KV_FORMATS = (None, "mxfp8", "paged")
 
 
 def build_kv_caches(n_layers: int, batch: int, n_kv_heads_local: int,
                     max_seq: int, head_dim: int, dtype=torch.bfloat16,
-                    device=None, window=None, kv_format=None
+                    device=None, window=None, kv_format=None, page_pool=None
                     ) -> List[KVCache]:
     """``window``: sliding-window models get RollingKVCache (O(window)
     memory per layer) when the window is smaller than max_seq.
@@ -90,10 +90,23 @@ def build_kv_caches(n_layers: int, batch: int, n_kv_heads_local: int,
     ``kv_format``: None stores K/V in ``dtype``; "mxfp8" returns
     :class:`MXKVCache` (e4m3 payload + e8m0 block scales, 0.516 of the bf16
     bytes) with ``dtype`` as the compute dtype.  The rolling cache has no
-    MX form."""
+    MX form.  "paged" returns :class:`PagedKVCache` layers on the
+    :class:`PagePool` ``page_pool``, whose table all layers share; it has
+    no rolling form either."""
     if kv_format not in KV_FORMATS:
         raise ValueError(f"kv_format {kv_format!r} not supported (one of "
                          f"{KV_FORMATS})")
+    if kv_format == "paged":
+        if window is not None and window < max_seq:
+            raise NotImplementedError(
+                "kv_format='paged' with a sliding window smaller than "
+                "max_seq: the rolling cache has no paged form")
+        if page_pool is None or page_pool.batch != batch:
+            raise ValueError(f"kv_format='paged' needs a page_pool for a "
+                             f"batch of {batch}")
+        return [PagedKVCache(page_pool, n_kv_heads_local, head_dim, dtype,
+                             device)
+                for _ in range(n_layers)]
     if kv_format == "mxfp8":
         if window is not None and window < max_seq:
             raise NotImplementedError(
@@ -260,3 +273,163 @@ class MXKVCache(KVCache):
         end = pos + S
         return (self._dequantize(self.k[:, :, :end], self.k_scale[:, :, :end]),
                 self._dequantize(self.v[:, :, :end], self.v_scale[:, :, :end]))
+
+
+PAGE_ROWS = 16   # rows of a page; PG_ROWS of ops/csrc/paged_attn.hip
+
+
+class PagePool:
+    """``num_pages`` pages of PAGE_ROWS cache rows, shared by ``batch``
+    sequences of at most ``pages_per_seq`` pages each.
+
+    ``block_table`` int32 (batch, pages_per_seq) on the device is the one
+    table all layers' :class:`PagedKVCache` read: entry [b, j] is the pool
+    page of rows [16 j, 16 j + 16) of sequence b, -1 = not allocated.  The
+    free list lives on the host; ``allocate`` and ``release`` ``copy_`` the
+    new table into the same device buffer, so a captured hipGraph sees the
+    update."""
+
+    def __init__(self, num_pages: int, batch: int, pages_per_seq: int,
+                 device=None):
+        if min(num_pages, batch, pages_per_seq) < 1:
+            raise ValueError(f"PagePool({num_pages}, {batch}, "
+                             f"{pages_per_seq}): sizes must be positive")
+        device = device or (torch.device("cuda") if torch.cuda.is_available()
+                            else "cpu")
+        self.num_pages, self.batch = num_pages, batch
+        self.pages_per_seq = pages_per_seq
+        self._host = torch.full((batch, pages_per_seq), -1, dtype=torch.int32)
+        self.block_table = self._host.to(device)
+        self._free = list(range(num_pages - 1, -1, -1))  # page 0 goes first
+        self._held = [0] * batch   # pages of each sequence
+
+    @property
+    def num_free(self) -> int:
+        return len(self._free)
+
+    def allocate(self, b: int, n_rows: int) -> None:
+        """Grow sequence ``b`` to cover rows [0, n_rows); raises, changing
+        nothing, if the table row or the pool cannot hold them."""
+        need = -(-int(n_rows) // PAGE_ROWS)
+        if need > self.pages_per_seq:
+            raise ValueError(f"{n_rows} rows need {need} pages, a sequence "
+                             f"holds at most {self.pages_per_seq}")
+        grow = need - self._held[b]
+        if grow <= 0:
+            return
+        if grow > len(self._free):
+            raise RuntimeError(f"PagePool out of pages: sequence {b} needs "
+                               f"{grow} more, {len(self._free)} of "
+                               f"{self.num_pages} are free")
+        for j in range(self._held[b], need):
+            self._host[b, j] = self._free.pop()
+        self._held[b] = need
+        self.block_table.copy_(self._host)
+
+    def release(self, b: int) -> None:
+        """Return the pages of sequence ``b``; its entries become -1."""
+        self._free.extend(reversed(self._host[b, :self._held[b]].tolist()))
+        self._host[b] = -1
+        self._held[b] = 0
+        self.block_table.copy_(self._host)
+
+
+class PagedKVCache:
+    """One layer's K/V in the pages of a :class:`PagePool`: ``k_pages``,
+    ``v_pages`` (num_pages, Hkv, PAGE_ROWS, D), addressed through the pool's
+    ``block_table``.  A sequence holds only the pages it was allocated, not
+    max_seq rows.
+
+    No table entry is trusted, here as in the kernels (ops.paged_attn_step,
+    ops.paged_kv_store): a prefill row whose page entry lies outside
+    [0, num_pages) is skipped, and a decode write of S rows at ``pos[b]``
+    happens only for an ACTIVE sequence (:meth:`active`).
+
+    bf16 GPU tensors with D = 128 are stored by the native kernels; CPU
+    tensors and other dtypes go through gather / scatter, the reference."""
+
+    def __init__(self, pool: PagePool, n_kv_heads: int, head_dim: int,
+                 dtype=torch.bfloat16, device=None):
+        self.pool = pool
+        device = device or pool.block_table.device
+        # one page more than the pool: where the reference path sends the
+        # writes it skips, so that its scatter keeps one static shape
+        self._k = torch.zeros(pool.num_pages + 1, n_kv_heads, PAGE_ROWS,
+                              head_dim, dtype=dtype, device=device)
+        self._v = torch.zeros_like(self._k)
+        self.k_pages = self._k[:pool.num_pages]
+        self.v_pages = self._v[:pool.num_pages]
+        self.max_seq = PAGE_ROWS * pool.pages_per_seq
+
+    def _valid(self) -> torch.Tensor:
+        """(B, pages_per_seq): the table entries that name a pool page."""
+        t = self.pool.block_table
+        return (t >= 0) & (t < self.pool.num_pages)
+
+    def active(self, pos: torch.Tensor, S: int = 1) -> torch.Tensor:
+        """(B,) bool for S new rows at ``pos`` (B,): all of them inside
+        [0, 16 * pages_per_seq) and every table entry up to the page of the
+        last one valid.  No host sync."""
+        pps = self.pool.pages_per_seq
+        pos = pos.reshape(-1, 1)
+        last = torch.div(pos + S - 1, PAGE_ROWS, rounding_mode="floor")
+        beyond = torch.arange(pps, device=pos.device).view(1, pps) > last
+        ok = (self._valid() | beyond).all(dim=1)
+        return ok & (pos[:, 0] >= 0) & (pos[:, 0] + S <= self.max_seq)
+
+    def _scatter(self, k_new, v_new, rows, ok) -> None:
+        """The reference write: k_new/v_new (B, Hkv, S, D) to rows (B, S) of
+        their sequences where ``ok`` (B, S) and the row's page is valid; the
+        rest lands in the spare page.  No host sync."""
+        pps, n = self.pool.pages_per_seq, self.pool.num_pages
+        j = torch.div(rows, PAGE_ROWS, rounding_mode="floor")
+        ok = ok & (j >= 0) & (j < pps)
+        j = j.clamp(0, pps - 1)
+        ok = ok & self._valid().gather(1, j)
+        page = torch.where(ok, self.pool.block_table.gather(1, j).long(), n)
+        slot = rows % PAGE_ROWS
+        self._k[page, :, slot] = k_new.permute(0, 2, 1, 3).to(self._k.dtype)
+        self._v[page, :, slot] = v_new.permute(0, 2, 1, 3).to(self._v.dtype)
+
+    def update(self, k_new: torch.Tensor, v_new: torch.Tensor, pos):
+        """k_new, v_new (B, Hkv, S, D).  An int ``pos`` of 0 is the prefill:
+        rows [0, S) go to their pages and (k_new, v_new) come back for the
+        flash kernel.  A (B,) tensor is the decode write of the active
+        sequences at ``pos[b] + s`` (one element counts for every sequence);
+        it returns :meth:`gather`.  An int ``pos`` > 0 has no paged form."""
+        B, _, S, D = k_new.shape
+        dev = k_new.device
+        if isinstance(pos, torch.Tensor):
+            pos = pos.reshape(-1).expand(B)
+            rows = pos.view(B, 1) + torch.arange(S, device=dev)
+            self._scatter(k_new, v_new, rows,
+                          self.active(pos, S).view(B, 1).expand(B, S))
+            return self.gather()
+        if pos != 0:
+            raise NotImplementedError(
+                "PagedKVCache takes a one-shot prefill from pos 0, then "
+                "device-tensor positions")
+        if k_new.is_cuda and D == 128 and k_new.dtype == torch.bfloat16 \
+                and self._k.dtype == torch.bfloat16:
+            from .. import ops
+
+            ops.paged_kv_store(k_new, v_new, self.k_pages, self.v_pages,
+                               self.pool.block_table, 0)
+        else:
+            rows = torch.arange(S, device=dev).expand(B, S)
+            self._scatter(k_new, v_new, rows, rows >= 0)
+        return k_new, v_new
+
+    def gather(self):
+        """Dense (B, Hkv, 16 * pages_per_seq, D) copies of K and V built
+        from the table; pages without a valid entry read as zeros."""
+        t = self.pool.block_table
+        B, pps = t.shape
+        valid = self._valid().view(B, 1, pps, 1, 1)
+        idx = t.clamp(0, self.pool.num_pages - 1).long()
+        out = []
+        for pages in (self.k_pages, self.v_pages):
+            x = pages[idx].transpose(1, 2)   # (B, Hkv, pps, 16, D)
+            x = torch.where(valid, x, 0)
+            out.append(x.reshape(B, x.shape[1], self.max_seq, x.shape[4]))
+        return tuple(out)

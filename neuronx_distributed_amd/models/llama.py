@@ -258,18 +258,47 @@ class LlamaAttention(nn.Module):
         own rows.  It is fused under the same conditions where
         ops.ragged_attn_enabled().  A sequence with pos_t[b] < 0 or
         pos_t[b] + S beyond the cache is inactive: its cache rows stay and
-        its attention output is zero on both paths."""
-        from ..inference.kv_cache import KVCache, MXKVCache
+        its attention output is zero on both paths.
+
+        A PagedKVCache always works with one position per sequence (one
+        element counts for every sequence).  S = 1 under the conditions
+        above goes through ops.paged_attn_step where
+        ops.paged_attn_available(); everything else takes the torch chain on
+        kv_cache.gather() after the paged write.  Activity is then
+        PagedKVCache.active: the position rule plus a valid page-table entry
+        for every page up to the new rows'."""
+        from ..inference.kv_cache import KVCache, MXKVCache, PagedKVCache
 
         B, S = q.shape[0], q.shape[1]
+        paged = type(kv_cache) is PagedKVCache
         ragged = B > 1 and pos_t.numel() == B
         if not ragged and pos_t.numel() != 1:
             raise ValueError(
                 f"a device-tensor position holds one element, or one per "
                 f"sequence ({B}), got {tuple(pos_t.shape)}")
+        if paged and not ragged:
+            pos_t, ragged = pos_t.reshape(1).expand(B), True
         rep = self.num_heads_local // self.num_kv_local
         scale = 1.0 / math.sqrt(self.head_dim)
         mx = type(kv_cache) is MXKVCache
+        if (paged and S == 1 and q.is_cuda and self.head_dim == 128
+                and rep in (1, 2, 4, 8) and q.dtype == torch.bfloat16
+                and self.sliding_window is None
+                and kv_cache.k_pages.dtype == torch.bfloat16
+                and kv_cache.k_pages.is_cuda and ops.paged_attn_available()):
+            def _flat(t):   # as for the dense one-token step below
+                t = t.squeeze(1)
+                f = t.reshape(B, -1)
+                return f if f.stride(1) == 1 else t.contiguous().view(B, -1)
+
+            out = ops.paged_attn_step(
+                _flat(q), _flat(k), _flat(v), kv_cache.k_pages,
+                kv_cache.v_pages, kv_cache.pool.block_table, cos, sin,
+                pos_t.reshape(B).contiguous(), self.num_heads_local,
+                self.num_kv_local, scale).unsqueeze(1)
+            if sp:
+                out = out.transpose(0, 1)
+            return self.o_proj(out)
         fusable = (q.is_cuda and self.head_dim == 128 and rep in (1, 2, 4, 8)
                    and q.dtype == torch.bfloat16
                    and self.sliding_window is None
@@ -331,9 +360,13 @@ class LlamaAttention(nn.Module):
                 raise NotImplementedError(
                     "per-sequence positions need a plain cache, not a "
                     "rolling one")
-            Smax = kv_cache.k.shape[2]
             pos_b = pos_t.reshape(B, 1)
-            active = (pos_b >= 0) & (pos_b + S <= Smax)       # (B, 1)
+            if paged:
+                Smax = kv_cache.max_seq
+                active = kv_cache.active(pos_b, S).view(B, 1)
+            else:
+                Smax = kv_cache.k.shape[2]
+                active = (pos_b >= 0) & (pos_b + S <= Smax)   # (B, 1)
             tpos = pos_b + torch.arange(S, device=q.device)   # (B, S)
             if cos.shape[0] < Smax:
                 raise ValueError(

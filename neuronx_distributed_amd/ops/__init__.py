@@ -1586,3 +1586,133 @@ def chunk_attn_mx_step(q3: torch.Tensor, k3: torch.Tensor, v3: torch.Tensor,
         fn, True, (q3, k3, v3, k_payload, k_scale, v_payload, v_scale, cos,
                    sin, pos_t),
         B, T, Hq, Hkv, Smax, scale, st)
+
+
+# ---------------------------------------------------------------------------
+# Paged KV cache: fused decode attention over a page pool + prefill store
+# (csrc/paged_attn.hip)
+# ---------------------------------------------------------------------------
+
+_PG_ROWS = 16   # PG_ROWS of csrc/paged_attn.hip: rows of a page
+
+
+def paged_attn_available() -> bool:
+    lib = _load()
+    return (lib is not None and hasattr(lib, "paged_decode_attn")
+            and hasattr(lib, "paged_kv_store"))
+
+
+def _paged_check_pools(who, k_pages, v_pages, block_table, B, Hkv):
+    """The two pools of a PagedKVCache, contiguous bf16 (num_pages, Hkv, 16,
+    128) on one GPU, and the table, contiguous int32 (B, >= 1) beside them.
+    Returns (num_pages, pages_per_seq)."""
+    for name, t in (("k_pages", k_pages), ("v_pages", v_pages)):
+        if t.dtype != torch.bfloat16 or t.dim() != 4 or not t.is_cuda \
+                or tuple(t.shape[1:]) != (Hkv, _PG_ROWS, _DA_D) \
+                or t.shape[0] < 1 or not t.is_contiguous():
+            raise ValueError(f"{who}: {name} must be a contiguous bf16 "
+                             f"(num_pages, {Hkv}, {_PG_ROWS}, {_DA_D}) GPU "
+                             f"pool, got {t.dtype} {tuple(t.shape)} strides "
+                             f"{t.stride()} on {t.device}")
+    if v_pages.shape != k_pages.shape or v_pages.device != k_pages.device:
+        raise ValueError(f"{who}: k_pages {tuple(k_pages.shape)} on "
+                         f"{k_pages.device} and v_pages "
+                         f"{tuple(v_pages.shape)} on {v_pages.device} must "
+                         f"be one shape on one GPU")
+    t = block_table
+    if t.dtype != torch.int32 or t.device != k_pages.device or t.dim() != 2 \
+            or t.shape[0] != B or t.shape[1] < 1 or not t.is_contiguous():
+        raise ValueError(f"{who}: block_table must be a contiguous int32 "
+                         f"({B}, >= 1) tensor on {k_pages.device}, got "
+                         f"{t.dtype} {tuple(t.shape)} strides {t.stride()} "
+                         f"on {t.device}")
+    return k_pages.shape[0], t.shape[1]
+
+
+def paged_attn_step(q2: torch.Tensor, k2: torch.Tensor, v2: torch.Tensor,
+                    k_pages: torch.Tensor, v_pages: torch.Tensor,
+                    block_table: torch.Tensor, cos: torch.Tensor,
+                    sin: torch.Tensor, pos_t: torch.Tensor, Hq: int, Hkv: int,
+                    scale: float) -> torch.Tensor:
+    """:func:`decode_attn_step` with ``ragged=True`` over a paged cache.
+    k_pages/v_pages bf16 (num_pages, Hkv, 16, 128); block_table int32
+    (B, pages_per_seq), entry [b, j] the pool page of rows [16 j, 16 j + 16)
+    of sequence b (-1: not allocated); cos/sin (>= 16 * pages_per_seq, 64)
+    fp32; pos_t int64 (B,) -> out (B, Hq*128).
+
+    Sequence b ropes its new row at ``pos_t[b]``, appends it to slot
+    ``pos_t[b] % 16`` of page ``block_table[b, pos_t[b] // 16]`` and attends
+    its rows [0, pos_t[b]].  It is inactive (pools untouched, output row
+    zero) unless ``0 <= pos_t[b] < 16 * pages_per_seq`` and every entry
+    ``block_table[b, 0 .. pos_t[b] // 16]`` lies in [0, num_pages): the
+    kernel checks the table, so a wrong one cannot make it leave the pools.
+    Shapes and dtypes are validated here without a device sync
+    (hipGraph-capturable); a wrong one raises ValueError and launches
+    nothing."""
+    lib = _require_lib()
+    who = "paged_attn_step"
+    if not paged_attn_available():
+        raise RuntimeError("nxd_ops library has no paged_decode_attn — "
+                           "rebuild")
+    B = q2.shape[0] if q2.dim() == 2 else -1
+    num_pages, pps = _paged_check_pools(who, k_pages, v_pages, block_table,
+                                        B, Hkv)
+    dev = k_pages.device
+    _, st = _decode_attn_check(who, False, q2, k2, v2, cos, sin, pos_t, B, Hq,
+                               Hkv, _PG_ROWS * pps, dev, ragged=True)
+    ws = _decode_attn_workspace(B, 1, Hq, Hkv, dev, False)
+    rc = lib.paged_decode_attn(
+        *map(_ptr, (q2, k2, v2, k_pages, v_pages, block_table, cos, sin,
+                    pos_t) + ws),
+        B, Hq, Hkv, num_pages, pps, ctypes.c_float(scale), *st, _stream())
+    if rc != 0:
+        raise ValueError(f"paged_decode_attn rejected B={B}, Hq={Hq}, "
+                         f"Hkv={Hkv}, num_pages={num_pages}, "
+                         f"pages_per_seq={pps}, strides {list(st)}")
+    return ws[2]
+
+
+def paged_kv_store(k: torch.Tensor, v: torch.Tensor, k_pages: torch.Tensor,
+                   v_pages: torch.Tensor, block_table: torch.Tensor,
+                   pos0: int = 0) -> None:
+    """Copy bf16 k, v (B, Hkv, S, 128) into the pages of rows
+    [pos0, pos0 + S) of every sequence in one launch.  k and v may be any
+    strided views with a dense last dim (the models hand in transposes of
+    (B, S, Hkv, D)); strides must be multiples of 8 elements.  A row beyond
+    the table, or whose table entry lies outside [0, num_pages), is skipped:
+    the right padding of a short prompt beyond its allocation falls away.
+    Contract violations raise ValueError and launch nothing."""
+    lib = _require_lib()
+    who = "paged_kv_store"
+    if not paged_attn_available():
+        raise RuntimeError("nxd_ops library has no paged_kv_store — rebuild")
+    if k.dim() != 4 or k.shape[2] < 1 or k.shape[3] != _DA_D \
+            or tuple(v.shape) != tuple(k.shape):
+        raise ValueError(f"{who}: k {tuple(k.shape)} / v {tuple(v.shape)} "
+                         f"must be one (B, Hkv, S >= 1, {_DA_D}) shape")
+    B, Hkv, S, _ = k.shape
+    num_pages, pps = _paged_check_pools(who, k_pages, v_pages, block_table,
+                                        B, Hkv)
+    dev = k_pages.device
+    pos0 = int(pos0)
+    if pos0 < 0:
+        raise ValueError(f"{who}: pos0 {pos0} is negative")
+    for name, t in (("k", k), ("v", v)):
+        if t.dtype != torch.bfloat16 or t.device != dev:
+            raise ValueError(f"{who}: {name} must be bf16 on {dev}, got "
+                             f"{t.dtype} on {t.device}")
+        if t.stride(3) != 1 or any(st < 0 or st % 8 for st in t.stride()[:3]) \
+                or t.data_ptr() % 16:
+            raise ValueError(f"{who}: {name} needs a dense last dim, strides "
+                             f"that are multiples of 8 and 16-byte "
+                             f"alignment, got strides {t.stride()}")
+    rc = lib.paged_kv_store(_ptr(k), _ptr(v),
+                            (ctypes.c_long * 4)(*k.stride()),
+                            (ctypes.c_long * 4)(*v.stride()),
+                            _ptr(k_pages), _ptr(v_pages), _ptr(block_table),
+                            B, Hkv, S, num_pages, pps, ctypes.c_long(pos0),
+                            _stream())
+    if rc != 0:
+        raise ValueError(f"paged_kv_store rejected k {tuple(k.shape)} strides "
+                         f"{k.stride()} at pos0 {pos0}, pools "
+                         f"{tuple(k_pages.shape)}")
