@@ -15,7 +15,7 @@ and rewrites rows in place, so stale rows are simply overwritten."""
 
 import torch
 
-from .kv_cache import build_kv_caches
+from .kv_cache import PAGE_ROWS, PagePool, build_kv_caches
 
 
 def _greedy(logits: torch.Tensor) -> torch.Tensor:
@@ -140,11 +140,21 @@ def speculative_generate(target, draft, input_ids: torch.Tensor,
     sequence that has its ``max_new_tokens`` goes inactive.  The result is
     laid out as by ``generate(prompt_lens=...)`` and the rate is accepted
     tokens over (active sequence-rounds x spec_len).  ``prompt_lens``
-    (per_sequence only): lengths of right-padded prompts, as in generate."""
+    (per_sequence only): lengths of right-padded prompts, as in generate.
+
+    ``kv_format="paged"`` (per_sequence only): each model gets one PagePool
+    of sum_b ceil((len_b + max_new_tokens + spec_len + 1) / 16) pages,
+    allocated up front.  On GPU the one-token draft steps then run through
+    ops.paged_attn_step, the draft's two-token step and the verify chunk
+    through ops.paged_chunk_attn_step."""
     if prompt_lens is not None and not per_sequence:
         raise ValueError("prompt_lens needs per_sequence=True")
+    if kv_format == "paged" and not per_sequence:
+        raise ValueError("kv_format='paged' needs per_sequence=True: a paged "
+                         "cache keeps one position per sequence")
     B, S = input_ids.shape
     dev = input_ids.device
+    extra = max_new_tokens + spec_len + 1   # rows beyond a prompt
 
     def make_caches(model):
         cfg = model.config
@@ -153,10 +163,22 @@ def speculative_generate(target, draft, input_ids: torch.Tensor,
         tp = ps.get_tensor_model_parallel_size()
         kv_mult = max(1, tp // cfg.num_key_value_heads)
         n_kv_local = cfg.num_key_value_heads * kv_mult // tp
+        pool = None
+        if kv_format == "paged":
+            # as generate(): every sequence allocated up front, so the table
+            # is static; stale rows of a rejected chunk stay inside it
+            from .generation import check_prompt_lens
+
+            lens = check_prompt_lens(
+                [S] * B if prompt_lens is None else prompt_lens, input_ids)
+            rows = [n + extra for n in lens.tolist()]
+            pages = [-(-n // PAGE_ROWS) for n in rows]
+            pool = PagePool(sum(pages), B, max(pages), dev)
+            for b, n in enumerate(rows):
+                pool.allocate(b, n)
         return build_kv_caches(cfg.num_hidden_layers, B, n_kv_local,
-                               S + max_new_tokens + spec_len + 1,
-                               cfg.head_dim, device=input_ids.device,
-                               kv_format=kv_format)
+                               S + extra, cfg.head_dim, device=dev,
+                               kv_format=kv_format, page_pool=pool)
 
     t_caches = make_caches(target)
     d_caches = make_caches(draft)

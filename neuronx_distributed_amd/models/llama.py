@@ -261,12 +261,14 @@ class LlamaAttention(nn.Module):
         its attention output is zero on both paths.
 
         A PagedKVCache always works with one position per sequence (one
-        element counts for every sequence).  S = 1 under the conditions
-        above goes through ops.paged_attn_step where
-        ops.paged_attn_available(); everything else takes the torch chain on
-        kv_cache.gather() after the paged write.  Activity is then
-        PagedKVCache.active: the position rule plus a valid page-table entry
-        for every page up to the new rows'."""
+        element counts for every sequence).  Under the conditions above
+        S = 1 goes through ops.paged_attn_step where
+        ops.paged_attn_available(), and S = 2..8 through
+        ops.paged_chunk_attn_step where ops.paged_chunk_attn_available() as
+        well; everything else takes the torch chain on kv_cache.gather()
+        after the paged write.  Activity is PagedKVCache.active on every
+        path: the position rule plus a valid page-table entry for every page
+        up to the new rows'."""
         from ..inference.kv_cache import KVCache, MXKVCache, PagedKVCache
 
         B, S = q.shape[0], q.shape[1]
@@ -281,21 +283,44 @@ class LlamaAttention(nn.Module):
         rep = self.num_heads_local // self.num_kv_local
         scale = 1.0 / math.sqrt(self.head_dim)
         mx = type(kv_cache) is MXKVCache
-        if (paged and S == 1 and q.is_cuda and self.head_dim == 128
-                and rep in (1, 2, 4, 8) and q.dtype == torch.bfloat16
-                and self.sliding_window is None
-                and kv_cache.k_pages.dtype == torch.bfloat16
-                and kv_cache.k_pages.is_cuda and ops.paged_attn_available()):
-            def _flat(t):   # as for the dense one-token step below
+        if S == 1:
+            def _flat(t):
+                # (B,1,h,D) -> (B, h*D) as a VIEW even for fused-QKV
+                # slices (batch stride may exceed h*D; decode_attn takes
+                # strides)
                 t = t.squeeze(1)
                 f = t.reshape(B, -1)
-                return f if f.stride(1) == 1 else t.contiguous().view(B, -1)
+                return f if f.stride(1) == 1 \
+                    else t.contiguous().view(B, -1)
+        else:
+            def _flat(t):
+                # (B,S,h,D) -> (B,S,h*D) as a VIEW of a fused-QKV slice
+                # where its strides allow (the kernels take row strides)
+                f = t.reshape(B, S, -1)
+                ok = (f.stride(2) == 1 and f.stride(1) >= f.shape[2]
+                      and f.stride(0) % 8 == 0 and f.stride(1) % 8 == 0
+                      and f.data_ptr() % 16 == 0)
+                return f if ok else f.contiguous()
 
-            out = ops.paged_attn_step(
-                _flat(q), _flat(k), _flat(v), kv_cache.k_pages,
-                kv_cache.v_pages, kv_cache.pool.block_table, cos, sin,
-                pos_t.reshape(B).contiguous(), self.num_heads_local,
-                self.num_kv_local, scale).unsqueeze(1)
+        fusable = (paged and q.is_cuda and self.head_dim == 128
+                   and rep in (1, 2, 4, 8) and q.dtype == torch.bfloat16
+                   and self.sliding_window is None
+                   and kv_cache.k_pages.dtype == torch.bfloat16
+                   and kv_cache.k_pages.is_cuda and ops.paged_attn_available())
+        if fusable and S > 1:
+            fusable = ops.paged_chunk_attn_available()
+        if fusable:
+            qf, kf, vf = _flat(q), _flat(k), _flat(v)
+            if S > 1 and kf.stride() != vf.stride():
+                kf, vf = kf.contiguous(), vf.contiguous()
+            step = ops.paged_attn_step if S == 1 \
+                else ops.paged_chunk_attn_step
+            out = step(qf, kf, vf, kv_cache.k_pages, kv_cache.v_pages,
+                       kv_cache.pool.block_table, cos, sin,
+                       pos_t.reshape(B).contiguous(), self.num_heads_local,
+                       self.num_kv_local, scale)
+            if S == 1:
+                out = out.unsqueeze(1)  # (B, 1, H*D)
             if sp:
                 out = out.transpose(0, 1)
             return self.o_proj(out)
@@ -317,25 +342,6 @@ class LlamaAttention(nn.Module):
             if ragged:
                 fusable = fusable and ops.ragged_attn_enabled()
         if fusable:
-            if S == 1:
-                def _flat(t):
-                    # (B,1,h,D) -> (B, h*D) as a VIEW even for fused-QKV
-                    # slices (batch stride may exceed h*D; decode_attn takes
-                    # strides)
-                    t = t.squeeze(1)
-                    f = t.reshape(B, -1)
-                    return f if f.stride(1) == 1 \
-                        else t.contiguous().view(B, -1)
-            else:
-                def _flat(t):
-                    # (B,S,h,D) -> (B,S,h*D) as a VIEW of a fused-QKV slice
-                    # where its strides allow (the kernels take row strides)
-                    f = t.reshape(B, S, -1)
-                    ok = (f.stride(2) == 1 and f.stride(1) >= f.shape[2]
-                          and f.stride(0) % 8 == 0 and f.stride(1) % 8 == 0
-                          and f.data_ptr() % 16 == 0)
-                    return f if ok else f.contiguous()
-
             qf, kf, vf = _flat(q), _flat(k), _flat(v)
             if S > 1 and kf.stride() != vf.stride():
                 kf, vf = kf.contiguous(), vf.contiguous()

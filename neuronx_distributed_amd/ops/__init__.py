@@ -1590,7 +1590,7 @@ def chunk_attn_mx_step(q3: torch.Tensor, k3: torch.Tensor, v3: torch.Tensor,
 
 # ---------------------------------------------------------------------------
 # Paged KV cache: fused decode attention over a page pool + prefill store
-# (csrc/paged_attn.hip)
+# (csrc/paged_attn.hip), and its multi-token form (csrc/paged_chunk_attn.hip)
 # ---------------------------------------------------------------------------
 
 _PG_ROWS = 16   # PG_ROWS of csrc/paged_attn.hip: rows of a page
@@ -1669,6 +1669,56 @@ def paged_attn_step(q2: torch.Tensor, k2: torch.Tensor, v2: torch.Tensor,
         raise ValueError(f"paged_decode_attn rejected B={B}, Hq={Hq}, "
                          f"Hkv={Hkv}, num_pages={num_pages}, "
                          f"pages_per_seq={pps}, strides {list(st)}")
+    return ws[2]
+
+
+def paged_chunk_attn_available() -> bool:
+    lib = _load()
+    return lib is not None and hasattr(lib, "paged_chunk_attn")
+
+
+def paged_chunk_attn_step(q3: torch.Tensor, k3: torch.Tensor,
+                          v3: torch.Tensor, k_pages: torch.Tensor,
+                          v_pages: torch.Tensor, block_table: torch.Tensor,
+                          cos: torch.Tensor, sin: torch.Tensor,
+                          pos_t: torch.Tensor, Hq: int, Hkv: int,
+                          scale: float) -> torch.Tensor:
+    """The multi-token sibling of :func:`paged_attn_step`
+    (csrc/paged_chunk_attn.hip): T = 2..8 new tokens per sequence.  q3
+    (B, T, Hq*128), k3/v3 (B, T, Hkv*128) bf16 pre-rope as for
+    :func:`chunk_attn_step`; pools, table, cos/sin and pos_t as for
+    :func:`paged_attn_step` -> out (B, T, Hq*128).
+
+    Token t of sequence b is roped at ``pos_t[b] + t``, stored in slot
+    ``(pos_t[b] + t) % 16`` of page ``block_table[b, (pos_t[b] + t) // 16]``
+    and attends rows [0, pos_t[b] + t] as stored.  The sequence is inactive
+    (pools untouched, output rows zero) unless ``0 <= pos_t[b]``,
+    ``pos_t[b] + T <= 16 * pages_per_seq`` and every entry
+    ``block_table[b, 0 .. (pos_t[b] + T - 1) // 16]`` lies in
+    [0, num_pages); no entry beyond that page is read.  No device sync
+    (hipGraph-capturable); a wrong dtype or shape raises ValueError and
+    launches nothing."""
+    lib = _require_lib()
+    who = "paged_chunk_attn_step"
+    if not paged_chunk_attn_available():
+        raise RuntimeError("nxd_ops library has no paged_chunk_attn — "
+                           "rebuild")
+    B = q3.shape[0] if q3.dim() == 3 else -1
+    num_pages, pps = _paged_check_pools(who, k_pages, v_pages, block_table,
+                                        B, Hkv)
+    dev = k_pages.device
+    T, st = _decode_attn_check(who, True, q3, k3, v3, cos, sin, pos_t, B, Hq,
+                               Hkv, _PG_ROWS * pps, dev, ragged=True)
+    ws = _decode_attn_workspace(B, T, Hq, Hkv, dev, True)
+    rc = lib.paged_chunk_attn(
+        *map(_ptr, (q3, k3, v3, k_pages, v_pages, block_table, cos, sin,
+                    pos_t) + ws),
+        B, T, Hq, Hkv, num_pages, pps, ctypes.c_float(scale), *st, _stream())
+    if rc != 0:
+        raise ValueError(f"paged_chunk_attn rejected B={B}, T={T}, Hq={Hq}, "
+                         f"Hkv={Hkv}, num_pages={num_pages}, "
+                         f"pages_per_seq={pps}, strides "
+                         f"{[s.value for s in st]}")
     return ws[2]
 
 

@@ -68,17 +68,8 @@
 // (B*Hkv*DA_SPLIT, R, 128) fp32, part_ml (..., R, 2) = (m, l) in the exp2
 // domain, m = -1e30 for a split without rows, as in decode_attn_common.h.
 
-#include "decode_attn_common.h"
-#include "flash_common.h"
+#include "chunk_attn_common.h"  // shared with paged_chunk_attn.hip
 #include "mx_quant.h"
-
-#define CA_TMIN 2
-#define CA_TMAX 8
-#define CA_TILE 32                          // cache rows per tile
-#define CA_IMG_B (CA_TILE * IMG_ROW_B)      // one image: 8192 B
-#define CA_WAVE_B (2 * CA_IMG_B)            // K image, then V image
-#define CA_LDS_B (DA_WAVES * CA_WAVE_B)     // 65536 B
-#define CA_OPAD 132                         // floats per row of the merge tile
 
 // the device position, clamped to [-CA_TMAX, Smax]: outside that range no
 // row is written and the set of rows attended does not change any more
@@ -86,14 +77,6 @@ template <bool RAGGED>
 __device__ __forceinline__ int ca_pos(const long* pos_ptr, int b, int Smax) {
   const long p = da_pos<RAGGED>(pos_ptr, b);
   return (int)max(min(p, (long)Smax), -(long)CA_TMAX);
-}
-
-// compiler-level ordering of one wave's LDS writes and reads (the hardware
-// keeps a wave's LDS operations in order)
-__device__ __forceinline__ void ca_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // ---------------------------------------------------------------------------
@@ -156,14 +139,7 @@ chunk_attn_append(const short* __restrict__ kin, const short* __restrict__ vin,
 // ---------------------------------------------------------------------------
 // 2. phase 1.  Staging of one 32-row tile by one wave.
 // ---------------------------------------------------------------------------
-template <bool MX> struct CaRegs;
-template <> struct CaRegs<false> { uint4v k[8], v[8]; };
 template <> struct CaRegs<true> { uint4v k[4], v[4]; unsigned ks[4], vs[4]; };
-
-__device__ __forceinline__ uint4v ca_sel(bool ok, uint4v x) {
-  const uint4v z = {0, 0, 0, 0};
-  return ok ? x : z;
-}
 
 // bf16: lane l, step i owns row 4i + (l >> 4), 16-byte chunk l & 15.
 // Rows >= n read row n - 1 and are zeroed.
@@ -178,16 +154,6 @@ __device__ __forceinline__ void ca_load(CaRegs<false>& r, const void* kc,
     const long off = (head_row + (ok ? rr : n - 1)) * DA_D + 8 * (lane & 15);
     r.k[i] = ca_sel(ok, *(const uint4v*)((const short*)kc + off));
     r.v[i] = ca_sel(ok, *(const uint4v*)((const short*)vc + off));
-  }
-}
-
-__device__ __forceinline__ void ca_write(const CaRegs<false>& r, char* kimg,
-                                         char* vimg, int lane) {
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const int off = img_off(4 * i + (lane >> 4), lane & 15);
-    *(uint4v*)(kimg + off) = r.k[i];
-    *(uint4v*)(vimg + off) = r.v[i];
   }
 }
 
@@ -238,30 +204,6 @@ __device__ __forceinline__ void ca_write(const CaRegs<true>& r, char* kimg,
     *(uint4v*)(kimg + o1) = ca_deq8(r.k[i][2], r.k[i][3], ksc);
     *(uint4v*)(vimg + o0) = ca_deq8(r.v[i][0], r.v[i][1], vsc);
     *(uint4v*)(vimg + o1) = ca_deq8(r.v[i][2], r.v[i][3], vsc);
-  }
-}
-
-// RoPE of 8 dims d0..d0+7 (d0 < 64) and their partners d0+64.., rounded to
-// bf16 as the MFMA takes them
-__device__ __forceinline__ void ca_rope8(uint4v xlo, uint4v xhi,
-                                         const float* cs, const float* sn,
-                                         uint4v& olo, uint4v& ohi) {
-  float lo[8], hi[8];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int e = 2 * j + h;
-      const float x0 = bits2f((short)(h ? xlo[j] >> 16 : xlo[j] & 0xffff));
-      const float x1 = bits2f((short)(h ? xhi[j] >> 16 : xhi[j] & 0xffff));
-      lo[e] = x0 * cs[e] - x1 * sn[e];
-      hi[e] = x1 * cs[e] + x0 * sn[e];
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    olo[j] = pack_bf16x2(lo[2 * j], lo[2 * j + 1]);
-    ohi[j] = pack_bf16x2(hi[2 * j], hi[2 * j + 1]);
   }
 }
 
@@ -485,23 +427,6 @@ chunk_attn_part(const short* __restrict__ qin, const void* __restrict__ kc,
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-// The launch contract: da_launch_ok's, T in [2, 8] with Smax >= T, strides
-// that hold a row and keep the 16-byte loads aligned.
-static bool ca_launch_ok(const void* q, const void* k, const void* v,
-                         const void* cosp, const void* sinp, int B, int T,
-                         int Hq, int Hkv, int Smax, long q_bs, long q_ts,
-                         long kv_bs, long kv_ts) {
-  if (T < CA_TMIN || T > CA_TMAX || Smax < T) return false;
-  if (q_bs < 0 || kv_bs < 0 || q_ts > 0x7FFFFFFFL || kv_ts > 0x7FFFFFFFL ||
-      q_ts < 0 || kv_ts < 0)
-    return false;
-  if (!da_launch_ok(B, Hq, Hkv, Smax, (int)q_ts, (int)kv_ts)) return false;
-  if (q_bs % 8 || q_ts % 8) return false;
-  if (((uintptr_t)q | (uintptr_t)cosp | (uintptr_t)sinp) % 16) return false;
-  if (((uintptr_t)k | (uintptr_t)v) % 2) return false;
-  return (long)B * Hkv * T <= 0x7FFFFFFFL && (long)Smax + T < 0x7FFFFFFFL;
-}
-
 template <bool MX, bool RAGGED>
 static int ca_launch(const void* q, const void* k, const void* v, void* kc,
                      void* ksc, void* vc, void* vsc, const void* cosp,
