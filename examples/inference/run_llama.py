@@ -36,6 +36,9 @@ def main():
                    choices=["bf16", "mxfp8", "paged"],
                    help="KV-cache storage: the model dtype, MXFP8, or the "
                         "model dtype in a page pool")
+    p.add_argument("--prefill-chunk", type=int, default=None,
+                   help="with --kv-format paged: prefill the prompt in "
+                        "chunks of this many tokens (more than 8)")
     args = p.parse_args()
 
     os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
@@ -73,7 +76,8 @@ def main():
         out = generate(model, prompt, max_new_tokens=args.new_tokens,
                        sampler=sampler,
                        kv_format=None if args.kv_format == "bf16"
-                       else args.kv_format)
+                       else args.kv_format,
+                       prefill_chunk=args.prefill_chunk)
         if torch.cuda.is_available():
             torch.cuda.synchronize()
         dt = time.time() - t0

@@ -36,7 +36,8 @@ def ragged_output(input_ids: torch.Tensor, lens: torch.Tensor,
 
 def _generate_ragged(model, input_ids, prompt_lens, max_new_tokens, sampler,
                      eos_token_id, use_cuda_graph, kv_format, pad_token_id,
-                     n_kv_local, model_dtype, who="prompt_lens"):
+                     n_kv_local, model_dtype, who="prompt_lens",
+                     prefill_chunk=None):
     """generate() for right-padded prompts of different lengths: one padded
     prefill, then decode with one position per sequence.
 
@@ -47,6 +48,14 @@ def _generate_ragged(model, input_ids, prompt_lens, max_new_tokens, sampler,
     ends on a page boundary: the model's RoPE table must cover
     16 * ceil((len_b + max_new_tokens) / 16) rows, up to 15 more than the
     tokens need.
+
+    ``prefill_chunk=N`` (paged only): the prompt is prefilled in
+    ceil(S / N) forwards of N tokens instead of one of S.  Chunk c runs at
+    the per-sequence position min(c N, len_b) with
+    chunk_lens = clamp(len_b - c N, 0, N) real tokens, so the padding of a
+    short prompt costs nothing once the prompt has ended, and the first new
+    token of sequence b comes from the logits row of its last real token, in
+    the chunk that holds it.
 
     ``who``: the argument the caller chose this path with, for messages."""
     from .decode_graph import GraphDecoder
@@ -77,10 +86,15 @@ def _generate_ragged(model, input_ids, prompt_lens, max_new_tokens, sampler,
                              S + max_new_tokens, cfg.head_dim,
                              dtype=model_dtype, device=dev,
                              kv_format=kv_format, page_pool=pool)
-    # padding sits to the right: no real token attends it, and the cache rows
-    # it leaves at >= len_b are masked until a decode step overwrites them
-    logits = model(input_ids, kv_caches=caches, pos_offset=0)
-    next_tok = sampler(logits[torch.arange(B, device=dev), lens - 1])
+    if prefill_chunk is not None:
+        next_tok = _prefill_chunked(model, input_ids, lens, caches,
+                                    int(prefill_chunk), sampler)
+    else:
+        # padding sits to the right: no real token attends it, and the cache
+        # rows it leaves at >= len_b are masked until a decode step
+        # overwrites them
+        logits = model(input_ids, kv_caches=caches, pos_offset=0)
+        next_tok = sampler(logits[torch.arange(B, device=dev), lens - 1])
     new = [next_tok]
     if input_ids.is_cuda:
         dec = GraphDecoder(model, caches, start_pos=lens, batch=B, device=dev)
@@ -103,11 +117,36 @@ def _generate_ragged(model, input_ids, prompt_lens, max_new_tokens, sampler,
                          S + max_new_tokens, pad_token_id)
 
 
+def _prefill_chunked(model, input_ids, lens, caches, N, sampler):
+    """The prompt in ceil(S / N) forwards of N tokens at per-sequence device
+    positions (_generate_ragged); returns the first new token of every
+    sequence.  The last chunk is right-padded to N tokens: one static shape
+    for every forward."""
+    B, S = input_ids.shape
+    dev = input_ids.device
+    rows = torch.arange(B, device=dev)
+    next_tok = None
+    for c0 in range(0, S, N):
+        ids = input_ids[:, c0:c0 + N]
+        if ids.shape[1] < N:
+            ids = torch.cat([ids, ids.new_zeros(B, N - ids.shape[1])], dim=1)
+        n = (lens - c0).clamp(0, N)
+        logits = model(ids, kv_caches=caches, pos_offset=lens.clamp(max=c0),
+                       chunk_lens=n)
+        # sampled for every sequence (one call, static shapes), kept for those
+        # whose last real token lies in this chunk
+        tok = sampler(logits[rows, (n - 1).clamp(min=0)])
+        here = (lens > c0) & (lens <= c0 + N)
+        next_tok = tok if next_tok is None else torch.where(here, tok,
+                                                            next_tok)
+    return next_tok
+
+
 @torch.no_grad()
 def generate(model, input_ids: torch.Tensor, max_new_tokens: int = 32,
              sampler: Optional[Sampler] = None, eos_token_id: int = -1,
              use_cuda_graph: bool = True, kv_format=None, prompt_lens=None,
-             pad_token_id: int = 0):
+             pad_token_id: int = 0, prefill_chunk=None):
     """model: LlamaForCausalLM-compatible (vocab-parallel logits out).
     input_ids (B, S) on the model's device; returns (B, S+new).
 
@@ -122,7 +161,11 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int = 32,
     (inference.kv_cache.MXKVCache) instead of the model dtype;
     ``kv_format="paged"`` keeps it in a page pool sized for the sequences'
     own lengths (inference.kv_cache.PagedKVCache) and always returns the
-    ``prompt_lens`` layout (without ``prompt_lens``, every length is S)."""
+    ``prompt_lens`` layout (without ``prompt_lens``, every length is S).
+    ``prefill_chunk=N`` (with ``kv_format="paged"`` only, N > 8) prefills the
+    prompt in chunks of N tokens through the paged prefill kernel
+    (ops.paged_prefill_attn_step), which bounds the activation memory of a
+    long prompt; None is one prefill of the whole prompt."""
     from ..parallel import parallel_state as ps
     from .decode_graph import GraphDecoder
 
@@ -133,6 +176,13 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int = 32,
     kv_mult = max(1, tp // cfg.num_key_value_heads)
     n_kv_local = cfg.num_key_value_heads * kv_mult // tp
     model_dtype = next(model.parameters()).dtype
+    if prefill_chunk is not None:
+        if kv_format != "paged":
+            raise ValueError(f"prefill_chunk needs kv_format='paged', got "
+                             f"{kv_format!r}")
+        if int(prefill_chunk) <= 8:
+            raise ValueError(f"prefill_chunk {prefill_chunk} must exceed 8: "
+                             f"shorter chunks are decode steps")
     if prompt_lens is not None or kv_format == "paged":
         who = "prompt_lens"
         if prompt_lens is None:   # a paged cache has one position per sequence
@@ -140,7 +190,7 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int = 32,
         return _generate_ragged(model, input_ids, prompt_lens,
                                 max_new_tokens, sampler, eos_token_id,
                                 use_cuda_graph, kv_format, pad_token_id,
-                                n_kv_local, model_dtype, who)
+                                n_kv_local, model_dtype, who, prefill_chunk)
     caches = build_kv_caches(cfg.num_hidden_layers, B, n_kv_local,
                              S + max_new_tokens, cfg.head_dim,
                              dtype=model_dtype, device=input_ids.device,

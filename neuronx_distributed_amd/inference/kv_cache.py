@@ -366,16 +366,24 @@ class PagedKVCache:
         t = self.pool.block_table
         return (t >= 0) & (t < self.pool.num_pages)
 
-    def active(self, pos: torch.Tensor, S: int = 1) -> torch.Tensor:
+    def active(self, pos: torch.Tensor, S: int = 1,
+               chunk_lens=None) -> torch.Tensor:
         """(B,) bool for S new rows at ``pos`` (B,): all of them inside
         [0, 16 * pages_per_seq) and every table entry up to the page of the
-        last one valid.  No host sync."""
+        last one valid.  No host sync.
+
+        ``chunk_lens`` (B,): only the first ``n[b] = chunk_lens[b]`` of the S
+        rows are real (chunked prefill).  ``n[b]`` then takes the place of S
+        and must lie in [1, S]; ``n[b] = 0`` is inactive."""
         pps = self.pool.pages_per_seq
         pos = pos.reshape(-1, 1)
-        last = torch.div(pos + S - 1, PAGE_ROWS, rounding_mode="floor")
+        n = S if chunk_lens is None else chunk_lens.reshape(-1, 1)
+        last = torch.div(pos + n - 1, PAGE_ROWS, rounding_mode="floor")
         beyond = torch.arange(pps, device=pos.device).view(1, pps) > last
         ok = (self._valid() | beyond).all(dim=1)
-        return ok & (pos[:, 0] >= 0) & (pos[:, 0] + S <= self.max_seq)
+        if chunk_lens is not None:
+            ok = ok & (n[:, 0] >= 1) & (n[:, 0] <= S)
+        return ok & (pos[:, 0] >= 0) & ((pos + n)[:, 0] <= self.max_seq)
 
     def _scatter(self, k_new, v_new, rows, ok) -> None:
         """The reference write: k_new/v_new (B, Hkv, S, D) to rows (B, S) of
@@ -391,20 +399,31 @@ class PagedKVCache:
         self._k[page, :, slot] = k_new.permute(0, 2, 1, 3).to(self._k.dtype)
         self._v[page, :, slot] = v_new.permute(0, 2, 1, 3).to(self._v.dtype)
 
-    def update(self, k_new: torch.Tensor, v_new: torch.Tensor, pos):
+    def update(self, k_new: torch.Tensor, v_new: torch.Tensor, pos,
+               chunk_lens=None):
         """k_new, v_new (B, Hkv, S, D).  An int ``pos`` of 0 is the prefill:
         rows [0, S) go to their pages and (k_new, v_new) come back for the
         flash kernel.  A (B,) tensor is the decode write of the active
         sequences at ``pos[b] + s`` (one element counts for every sequence);
-        it returns :meth:`gather`.  An int ``pos`` > 0 has no paged form."""
+        it returns :meth:`gather`.  An int ``pos`` > 0 has no paged form.
+
+        ``chunk_lens`` (B,), with a tensor ``pos`` only: the chunked-prefill
+        write of the first ``chunk_lens[b]`` rows of each sequence that is
+        active by :meth:`active` with the same argument; the other rows are
+        padding and nothing is stored for them."""
         B, _, S, D = k_new.shape
         dev = k_new.device
         if isinstance(pos, torch.Tensor):
             pos = pos.reshape(-1).expand(B)
-            rows = pos.view(B, 1) + torch.arange(S, device=dev)
-            self._scatter(k_new, v_new, rows,
-                          self.active(pos, S).view(B, 1).expand(B, S))
+            steps = torch.arange(S, device=dev)
+            rows = pos.view(B, 1) + steps
+            ok = self.active(pos, S, chunk_lens).view(B, 1).expand(B, S)
+            if chunk_lens is not None:
+                ok = ok & (steps < chunk_lens.reshape(B, 1))
+            self._scatter(k_new, v_new, rows, ok)
             return self.gather()
+        if chunk_lens is not None:
+            raise ValueError("chunk_lens needs a device-tensor position")
         if pos != 0:
             raise NotImplementedError(
                 "PagedKVCache takes a one-shot prefill from pos 0, then "

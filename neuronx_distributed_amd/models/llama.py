@@ -194,7 +194,12 @@ class LlamaAttention(nn.Module):
             bias=False, input_is_parallel=True, sequence_parallel_enabled=sp,
             init_method=_init_method(config.initializer_range))
 
-    def forward(self, hidden, cos, sin, pos_offset=0, kv_cache=None):
+    def forward(self, hidden, cos, sin, pos_offset=0, kv_cache=None,
+                chunk_lens=None):
+        """``chunk_lens`` (B,) int64 on the device: chunked prefill on a
+        PagedKVCache.  Only the first chunk_lens[b] of the S > 8 tokens at the
+        device-tensor position are real, the others are padding
+        (:meth:`_cached_step`)."""
         sp = self.config.sequence_parallel_enabled
         q, k, v = self.qkv_proj(hidden)
         if sp:
@@ -208,13 +213,23 @@ class LlamaAttention(nn.Module):
             # hipGraph-capturable decode: device-tensor position, S == 1
             # (or a chunk of 2..8 tokens: speculative verification),
             # full-cache masked attention (no dynamic shapes)
-            if not 1 <= S <= 8:
+            from ..inference.kv_cache import PagedKVCache
+
+            # a longer chunk: chunked prefill, on a paged cache only
+            if not 1 <= S <= 8 and (S < 1
+                                    or type(kv_cache) is not PagedKVCache):
                 raise ValueError(
                     f"a device-tensor position takes 1..8 tokens per "
                     f"forward, got {S}; use an int position for a longer "
                     f"chunk")
+            if chunk_lens is not None and S <= 8:
+                raise ValueError(
+                    f"chunk_lens goes with a chunk of more than 8 tokens, "
+                    f"got {S}: the steps of 1..8 tokens have no padding")
             return self._cached_step(q, k, v, cos, sin, pos_offset, kv_cache,
-                                     sp)
+                                     sp, chunk_lens)
+        if chunk_lens is not None:
+            raise ValueError("chunk_lens needs a device-tensor position")
         q, k = ops.apply_rotary_pos_emb(q, k, cos, sin, pos_offset)
 
         # (B,S,h,D) -> (B,h,S,D)
@@ -239,7 +254,8 @@ class LlamaAttention(nn.Module):
             out = out.transpose(0, 1)
         return self.o_proj(out)
 
-    def _cached_step(self, q, k, v, cos, sin, pos_t, kv_cache, sp):
+    def _cached_step(self, q, k, v, cos, sin, pos_t, kv_cache, sp,
+                     chunk_lens=None):
         """S = 1..8 new tokens at the device position ``pos_t`` (shape (1,)):
         token t is roped at pos + t, written to cache row pos + t and attends
         rows [0, pos + t].  Everything derives from the device tensor, so the
@@ -268,7 +284,15 @@ class LlamaAttention(nn.Module):
         well; everything else takes the torch chain on kv_cache.gather()
         after the paged write.  Activity is PagedKVCache.active on every
         path: the position rule plus a valid page-table entry for every page
-        up to the new rows'."""
+        up to the new rows'.
+
+        S > 8 on a PagedKVCache is the chunked prefill: with ``chunk_lens``
+        only the first n[b] = chunk_lens[b] tokens of sequence b are real and
+        n[b] takes the place of S in the activity rule (n[b] = 0: inactive).
+        Padding tokens store nothing and their outputs are zero, like those
+        of an inactive sequence.  It goes through ops.paged_prefill_attn_step
+        where ops.paged_prefill_attn_available() under the conditions above,
+        and through the torch chain otherwise."""
         from ..inference.kv_cache import KVCache, MXKVCache, PagedKVCache
 
         B, S = q.shape[0], q.shape[1]
@@ -307,7 +331,9 @@ class LlamaAttention(nn.Module):
                    and self.sliding_window is None
                    and kv_cache.k_pages.dtype == torch.bfloat16
                    and kv_cache.k_pages.is_cuda and ops.paged_attn_available())
-        if fusable and S > 1:
+        if fusable and S > 8:
+            fusable = ops.paged_prefill_attn_available()
+        elif fusable and S > 1:
             fusable = ops.paged_chunk_attn_available()
         if fusable:
             qf, kf, vf = _flat(q), _flat(k), _flat(v)
@@ -315,10 +341,15 @@ class LlamaAttention(nn.Module):
                 kf, vf = kf.contiguous(), vf.contiguous()
             step = ops.paged_attn_step if S == 1 \
                 else ops.paged_chunk_attn_step
+            more = ()
+            if S > 8:
+                step = ops.paged_prefill_attn_step
+                more = (None if chunk_lens is None
+                        else chunk_lens.reshape(B).contiguous(),)
             out = step(qf, kf, vf, kv_cache.k_pages, kv_cache.v_pages,
                        kv_cache.pool.block_table, cos, sin,
                        pos_t.reshape(B).contiguous(), self.num_heads_local,
-                       self.num_kv_local, scale)
+                       self.num_kv_local, scale, *more)
             if S == 1:
                 out = out.unsqueeze(1)  # (B, 1, H*D)
             if sp:
@@ -369,16 +400,20 @@ class LlamaAttention(nn.Module):
             pos_b = pos_t.reshape(B, 1)
             if paged:
                 Smax = kv_cache.max_seq
-                active = kv_cache.active(pos_b, S).view(B, 1)
+                active = kv_cache.active(pos_b, S, chunk_lens).view(B, 1)
             else:
                 Smax = kv_cache.k.shape[2]
                 active = (pos_b >= 0) & (pos_b + S <= Smax)   # (B, 1)
             tpos = pos_b + torch.arange(S, device=q.device)   # (B, S)
+            if chunk_lens is not None:   # (B, S): the real tokens
+                active = active & (torch.arange(S, device=q.device)
+                                   < chunk_lens.reshape(B, 1))
             if cos.shape[0] < Smax:
                 raise ValueError(
                     f"the RoPE table ({cos.shape[0]} rows) must cover the "
                     f"cache ({Smax} rows)")
-            # an inactive sequence ropes at row 0; its output is zeroed below
+            # an inactive sequence (a padding token) ropes at row 0; its
+            # output is zeroed below
             rows = torch.where(active, tpos, 0).reshape(-1)
             c = cos.index_select(0, rows).view(B, S, 1, half)
             s = sin.index_select(0, rows).view(B, S, 1, half)
@@ -398,7 +433,9 @@ class LlamaAttention(nn.Module):
         q = rope(q).transpose(1, 2)  # (B,h,S,D)
         k = rope(k).transpose(1, 2)
         v = v.transpose(1, 2)
-        K, V = kv_cache.update(k, v, pos_t)  # FULL (B,Hkv,Smax,D) buffers
+        # FULL (B,Hkv,Smax,D) buffers
+        K, V = kv_cache.update(k, v, pos_t) if chunk_lens is None \
+            else kv_cache.update(k, v, pos_t, chunk_lens)
         if K.dtype != q.dtype:  # a cache kept in another dtype than the model
             K, V = K.to(q.dtype), V.to(q.dtype)
         Smax = K.shape[2]
@@ -421,7 +458,8 @@ class LlamaAttention(nn.Module):
         if ragged:
             # an inactive sequence at a negative position would mask every
             # row: let it see row 0, its output is zeroed anyway
-            invalid = invalid & ~((idx == 0) & ~active.view(B, 1, 1, 1, 1))
+            invalid = invalid & ~((idx == 0)
+                                  & ~active.view(B, 1, 1, -1, 1))
         scores = scores.masked_fill(invalid, float("-inf"))
         probs = torch.softmax(scores, dim=-1).to(q.dtype)
         out = probs.view(B, self.num_kv_local, rep * S, Smax) @ V
@@ -429,7 +467,7 @@ class LlamaAttention(nn.Module):
         out = out.transpose(1, 2).reshape(B, S, -1)
         if ragged:
             # exact zeros, whatever the stale rows of the sequence hold
-            out = torch.where(active.view(B, 1, 1), out, 0)
+            out = torch.where(active.view(B, -1, 1), out, 0)
         if sp:
             out = out.transpose(0, 1)
         return self.o_proj(out)
@@ -495,12 +533,15 @@ class LlamaDecoderLayer(nn.Module):
             config.hidden_size, config.rms_norm_eps,
             sequence_parallel_enabled=sp)
 
-    def forward(self, hidden, cos, sin, pos_offset=0, kv_cache=None):
+    def forward(self, hidden, cos, sin, pos_offset=0, kv_cache=None,
+                chunk_lens=None):
         h = hidden + self.self_attn(self.input_layernorm(hidden), cos, sin,
-                                    pos_offset, kv_cache)
+                                    pos_offset, kv_cache,
+                                    chunk_lens=chunk_lens)
         return h + self.mlp(self.post_attention_layernorm(h))
 
-    def forward_fused(self, residual, delta, cos, sin, pos_offset, kv_cache):
+    def forward_fused(self, residual, delta, cos, sin, pos_offset, kv_cache,
+                      chunk_lens=None):
         """Inference path carrying (residual, delta) so every residual-add
         fuses into the next RMSNorm (ops.add_rmsnorm): 2 elementwise kernels
         per layer instead of 4.  hidden == residual + delta."""
@@ -510,7 +551,8 @@ class LlamaDecoderLayer(nn.Module):
             residual, normed = ops.add_rmsnorm(
                 residual, delta, self.input_layernorm.weight,
                 self.input_layernorm.variance_epsilon)
-        attn_out = self.self_attn(normed, cos, sin, pos_offset, kv_cache)
+        attn_out = self.self_attn(normed, cos, sin, pos_offset, kv_cache,
+                                  chunk_lens=chunk_lens)
         residual, normed2 = ops.add_rmsnorm(
             residual, attn_out, self.post_attention_layernorm.weight,
             self.post_attention_layernorm.variance_epsilon)
@@ -564,7 +606,11 @@ class LlamaModel(nn.Module):
             self.rope_cos.copy_(cos)
             self.rope_sin.copy_(sin)
 
-    def forward(self, input_ids, pos_offset=0, kv_caches=None):
+    def forward(self, input_ids, pos_offset=0, kv_caches=None,
+                chunk_lens=None):
+        # chunk_lens: LlamaAttention.forward; passed on only when given, so
+        # layers of other families keep their signatures
+        kw = {} if chunk_lens is None else {"chunk_lens": chunk_lens}
         hidden = self.embed_tokens(input_ids)  # (B,S,H)
         if self.config.sequence_parallel_enabled:
             hidden = hidden.transpose(0, 1).contiguous()  # (S,B,H)
@@ -584,7 +630,7 @@ class LlamaModel(nn.Module):
                 kc = kv_caches[i] if kv_caches is not None else None
                 residual, delta = layer.forward_fused(
                     residual, delta, self.rope_cos, self.rope_sin,
-                    pos_offset, kc)
+                    pos_offset, kc, **kw)
             _, hidden = ops.add_rmsnorm(residual, delta, self.norm.weight,
                                         self.norm.variance_epsilon)
             return hidden
@@ -612,7 +658,7 @@ class LlamaModel(nn.Module):
             for i, layer in enumerate(self.layers):
                 kc = kv_caches[i] if kv_caches is not None else None
                 hidden = layer(hidden, self.rope_cos, self.rope_sin,
-                               pos_offset, kc)
+                               pos_offset, kc, **kw)
             hidden = self.norm(hidden)
         if self.config.sequence_parallel_enabled:
             hidden = gather_from_sequence_parallel_region(
@@ -636,8 +682,11 @@ class LlamaForCausalLM(nn.Module):
         if config.tie_word_embeddings:
             self.lm_head.weight = self.model.embed_tokens.weight
 
-    def forward(self, input_ids, labels=None, pos_offset=0, kv_caches=None):
-        hidden = self.model(input_ids, pos_offset, kv_caches)
+    def forward(self, input_ids, labels=None, pos_offset=0, kv_caches=None,
+                chunk_lens=None):
+        hidden = self.model(input_ids, pos_offset, kv_caches,
+                            **({} if chunk_lens is None
+                               else {"chunk_lens": chunk_lens}))
         if labels is not None and self.config.loss_chunks > 0:
             from ..utils.chunked_loss import chunked_lm_loss
 

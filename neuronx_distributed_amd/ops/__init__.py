@@ -1590,7 +1590,8 @@ def chunk_attn_mx_step(q3: torch.Tensor, k3: torch.Tensor, v3: torch.Tensor,
 
 # ---------------------------------------------------------------------------
 # Paged KV cache: fused decode attention over a page pool + prefill store
-# (csrc/paged_attn.hip), and its multi-token form (csrc/paged_chunk_attn.hip)
+# (csrc/paged_attn.hip), its multi-token form (csrc/paged_chunk_attn.hip) and
+# the chunked prefill (csrc/paged_prefill_attn.hip)
 # ---------------------------------------------------------------------------
 
 _PG_ROWS = 16   # PG_ROWS of csrc/paged_attn.hip: rows of a page
@@ -1720,6 +1721,113 @@ def paged_chunk_attn_step(q3: torch.Tensor, k3: torch.Tensor,
                          f"pages_per_seq={pps}, strides "
                          f"{[s.value for s in st]}")
     return ws[2]
+
+
+def paged_prefill_attn_available() -> bool:
+    lib = _load()
+    return lib is not None and hasattr(lib, "paged_prefill_attn")
+
+
+def _paged_prefill_check(who, q3, k3, v3, cos, sin, pos_t, chunk_lens, B, Hq,
+                         Hkv, Smax, dev):
+    """q3/k3/v3, the RoPE table, pos_t and chunk_lens of
+    :func:`paged_prefill_attn_step`; no sync.  Returns T and the element
+    strides (q batch, q token, kv batch, kv token)."""
+    D = _DA_D
+    if Hkv < 1 or Hq % Hkv or Hq // Hkv not in (1, 2, 4, 8):
+        raise ValueError(f"{who}: Hq={Hq}, Hkv={Hkv} outside the kernel "
+                         f"contract (GQA rep 1/2/4/8)")
+    if q3.dim() != 3 or q3.shape[1] < 1:
+        raise ValueError(f"{who}: q3 {tuple(q3.shape)} must be "
+                         f"(B, T >= 1, Hq*128)")
+    T = q3.shape[1]
+    for name, t, width in (("q3", q3, Hq * D), ("k3", k3, Hkv * D),
+                           ("v3", v3, Hkv * D)):
+        ok = t.dtype == torch.bfloat16 and t.device == dev \
+            and tuple(t.shape) == (B, T, width) and t.stride(2) == 1 \
+            and t.stride(1) >= width and t.stride(0) >= 0 \
+            and not (t.stride(0) % 8 or t.stride(1) % 8) \
+            and t.data_ptr() % 16 == 0
+        if not ok:
+            raise ValueError(f"{who}: {name} must be a 16-byte aligned bf16 "
+                             f"{(B, T, width)} tensor on {dev} with a dense "
+                             f"last dim and strides that hold a row and are "
+                             f"multiples of 8, got {t.dtype} "
+                             f"{tuple(t.shape)} strides {t.stride()} on "
+                             f"{t.device}")
+    if k3.stride() != v3.stride():
+        raise ValueError(f"{who}: k3 and v3 must share their strides, got "
+                         f"{k3.stride()} and {v3.stride()}")
+    for name, t in (("cos", cos), ("sin", sin)):
+        _mx_check_dense(f"{who}: {name}", t, torch.float32)
+        if t.device != dev or t.dim() != 2 or t.shape[1] != D // 2 \
+                or t.shape[0] < Smax or t.data_ptr() % 16:
+            raise ValueError(f"{who}: {name} {tuple(t.shape)} on {t.device} "
+                             f"must be (>= {Smax}, {D // 2}) on {dev}: the "
+                             f"RoPE table covers the cache")
+    for name, t in (("pos_t", pos_t), ("chunk_lens", chunk_lens)):
+        if t is None and name == "chunk_lens":
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 \
+                or t.device != dev or tuple(t.shape) != (B,) \
+                or not t.is_contiguous():
+            raise ValueError(f"{who}: {name} must be a contiguous int64 "
+                             f"({B},) tensor on {dev}, got "
+                             f"{getattr(t, 'dtype', type(t))} "
+                             f"{tuple(getattr(t, 'shape', ()))}")
+    return T, tuple(ctypes.c_long(int(st)) for st in
+                    (q3.stride(0), q3.stride(1), k3.stride(0), k3.stride(1)))
+
+
+def paged_prefill_attn_step(q3: torch.Tensor, k3: torch.Tensor,
+                            v3: torch.Tensor, k_pages: torch.Tensor,
+                            v_pages: torch.Tensor, block_table: torch.Tensor,
+                            cos: torch.Tensor, sin: torch.Tensor,
+                            pos_t: torch.Tensor, Hq: int, Hkv: int,
+                            scale: float,
+                            chunk_lens: Optional[torch.Tensor] = None
+                            ) -> torch.Tensor:
+    """Chunked prefill over a paged cache (csrc/paged_prefill_attn.hip): any
+    T >= 1 new tokens per sequence, meant for T > 8, of which the first
+    ``chunk_lens[b]`` are real (None: all T).  q3 (B, T, Hq*128), k3/v3
+    (B, T, Hkv*128) bf16 pre-rope, possibly strided views of a fused-QKV
+    output; pools, table, cos/sin and pos_t as for :func:`paged_attn_step`;
+    chunk_lens int64 (B,) on the device -> out (B, T, Hq*128).
+
+    With n = chunk_lens[b]: token t < n of sequence b is roped at
+    ``pos_t[b] + t``, stored in slot ``(pos_t[b] + t) % 16`` of page
+    ``block_table[b, (pos_t[b] + t) // 16]`` and attends rows
+    [0, pos_t[b] + t] as stored.  Tokens t >= n are padding: nothing is
+    stored for them and their output rows are zero.  The sequence is inactive
+    (pools untouched, output rows zero) unless ``1 <= n <= T``,
+    ``0 <= pos_t[b]``, ``pos_t[b] + n <= 16 * pages_per_seq`` and every entry
+    ``block_table[b, 0 .. (pos_t[b] + n - 1) // 16]`` lies in [0, num_pages);
+    no entry beyond that page is read.  No device sync and no atomics
+    (hipGraph-capturable); a wrong dtype, shape, device or stride raises
+    ValueError and launches nothing."""
+    lib = _require_lib()
+    who = "paged_prefill_attn_step"
+    if not paged_prefill_attn_available():
+        raise RuntimeError("nxd_ops library has no paged_prefill_attn — "
+                           "rebuild")
+    B = q3.shape[0] if q3.dim() == 3 else -1
+    num_pages, pps = _paged_check_pools(who, k_pages, v_pages, block_table,
+                                        B, Hkv)
+    dev = k_pages.device
+    T, st = _paged_prefill_check(who, q3, k3, v3, cos, sin, pos_t, chunk_lens,
+                                 B, Hq, Hkv, _PG_ROWS * pps, dev)
+    out = torch.empty(B, T, Hq * _DA_D, dtype=torch.bfloat16, device=dev)
+    lens = ctypes.c_void_p(None) if chunk_lens is None else _ptr(chunk_lens)
+    rc = lib.paged_prefill_attn(
+        *map(_ptr, (q3, k3, v3, k_pages, v_pages, block_table, cos, sin,
+                    pos_t)), lens, _ptr(out),
+        B, T, Hq, Hkv, num_pages, pps, ctypes.c_float(scale), *st, _stream())
+    if rc != 0:
+        raise ValueError(f"paged_prefill_attn rejected B={B}, T={T}, Hq={Hq}, "
+                         f"Hkv={Hkv}, num_pages={num_pages}, "
+                         f"pages_per_seq={pps}, strides "
+                         f"{[s.value for s in st]}")
+    return out
 
 
 def paged_kv_store(k: torch.Tensor, v: torch.Tensor, k_pages: torch.Tensor,
