@@ -33,11 +33,12 @@ def main():
     p.add_argument("--new-tokens", type=int, default=128)
     p.add_argument("--top-k", type=int, default=0, help="0 = greedy")
     p.add_argument("--kv-format", default="bf16",
-                   choices=["bf16", "mxfp8", "paged"],
-                   help="KV-cache storage: the model dtype, MXFP8, or the "
-                        "model dtype in a page pool")
+                   choices=["bf16", "mxfp8", "paged", "paged_mxfp8"],
+                   help="KV-cache storage: the model dtype, MXFP8, the "
+                        "model dtype in a page pool, or MXFP8 in a page "
+                        "pool")
     p.add_argument("--prefill-chunk", type=int, default=None,
-                   help="with --kv-format paged: prefill the prompt in "
+                   help="with a paged --kv-format: prefill the prompt in "
                         "chunks of this many tokens (more than 8)")
     args = p.parse_args()
 

@@ -9,6 +9,8 @@ import torch
 from ..utils.sampling import Sampler
 from .kv_cache import PAGE_ROWS, PagePool, build_kv_caches
 
+PAGED_FORMATS = ("paged", "paged_mxfp8")   # one position per sequence
+
 
 def check_prompt_lens(prompt_lens, input_ids: torch.Tensor) -> torch.Tensor:
     """``prompt_lens`` ((B,) ints, tensor or list) as a device int64 (B,)
@@ -41,15 +43,15 @@ def _generate_ragged(model, input_ids, prompt_lens, max_new_tokens, sampler,
     """generate() for right-padded prompts of different lengths: one padded
     prefill, then decode with one position per sequence.
 
-    ``kv_format="paged"``: one PagePool of sum_b ceil((len_b +
-    max_new_tokens) / 16) pages, every sequence allocated up front, so the
+    ``kv_format="paged"`` or "paged_mxfp8": one PagePool of sum_b
+    ceil((len_b + max_new_tokens) / 16) pages, every sequence allocated up front, so the
     table is static while the decode graph replays; the prefill drops the
     padding rows beyond a sequence's pages.  The cache of a sequence then
     ends on a page boundary: the model's RoPE table must cover
     16 * ceil((len_b + max_new_tokens) / 16) rows, up to 15 more than the
     tokens need.
 
-    ``prefill_chunk=N`` (paged only): the prompt is prefilled in
+    ``prefill_chunk=N`` (paged formats only): the prompt is prefilled in
     ceil(S / N) forwards of N tokens instead of one of S.  Chunk c runs at
     the per-sequence position min(c N, len_b) with
     chunk_lens = clamp(len_b - c N, 0, N) real tokens, so the padding of a
@@ -76,7 +78,7 @@ def _generate_ragged(model, input_ids, prompt_lens, max_new_tokens, sampler,
         raise NotImplementedError(
             f"{who} needs a model that takes device-tensor positions")
     pool = None
-    if kv_format == "paged":
+    if kv_format in PAGED_FORMATS:
         rows = [n + max_new_tokens for n in lens.tolist()]
         pages = [-(-n // PAGE_ROWS) for n in rows]
         pool = PagePool(sum(pages), B, max(pages), dev)
@@ -162,10 +164,14 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int = 32,
     ``kv_format="paged"`` keeps it in a page pool sized for the sequences'
     own lengths (inference.kv_cache.PagedKVCache) and always returns the
     ``prompt_lens`` layout (without ``prompt_lens``, every length is S).
-    ``prefill_chunk=N`` (with ``kv_format="paged"`` only, N > 8) prefills the
+    ``kv_format="paged_mxfp8"`` is the paged cache with MXFP8 rows inside the
+    pages (inference.kv_cache.PagedMXKVCache), sized and laid out the same;
+    its one-token decode step is fused (ops.paged_attn_mx_step).
+    ``prefill_chunk=N`` (with a paged ``kv_format`` only, N > 8) prefills the
     prompt in chunks of N tokens through the paged prefill kernel
     (ops.paged_prefill_attn_step), which bounds the activation memory of a
-    long prompt; None is one prefill of the whole prompt."""
+    long prompt; None is one prefill of the whole prompt.  On
+    ``"paged_mxfp8"`` the chunks run on the reference path."""
     from ..parallel import parallel_state as ps
     from .decode_graph import GraphDecoder
 
@@ -177,16 +183,16 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int = 32,
     n_kv_local = cfg.num_key_value_heads * kv_mult // tp
     model_dtype = next(model.parameters()).dtype
     if prefill_chunk is not None:
-        if kv_format != "paged":
-            raise ValueError(f"prefill_chunk needs kv_format='paged', got "
-                             f"{kv_format!r}")
+        if kv_format not in PAGED_FORMATS:
+            raise ValueError(f"prefill_chunk needs kv_format='paged' or "
+                             f"'paged_mxfp8', got {kv_format!r}")
         if int(prefill_chunk) <= 8:
             raise ValueError(f"prefill_chunk {prefill_chunk} must exceed 8: "
                              f"shorter chunks are decode steps")
-    if prompt_lens is not None or kv_format == "paged":
+    if prompt_lens is not None or kv_format in PAGED_FORMATS:
         who = "prompt_lens"
         if prompt_lens is None:   # a paged cache has one position per sequence
-            prompt_lens, who = [S] * B, "kv_format='paged'"
+            prompt_lens, who = [S] * B, f"kv_format={kv_format!r}"
         return _generate_ragged(model, input_ids, prompt_lens,
                                 max_new_tokens, sampler, eos_token_id,
                                 use_cuda_graph, kv_format, pad_token_id,

@@ -77,7 +77,7 @@ def _ragged_write(pos: torch.Tensor, *pairs) -> None:
         buf.scatter_(2, idx, torch.where(active, new, buf.gather(2, idx)))
 
 
-KV_FORMATS = (None, "mxfp8", "paged")
+KV_FORMATS = (None, "mxfp8", "paged", "paged_mxfp8")
 
 
 def build_kv_caches(n_layers: int, batch: int, n_kv_heads_local: int,
@@ -92,20 +92,21 @@ def build_kv_caches(n_layers: int, batch: int, n_kv_heads_local: int,
     bytes) with ``dtype`` as the compute dtype.  The rolling cache has no
     MX form.  "paged" returns :class:`PagedKVCache` layers on the
     :class:`PagePool` ``page_pool``, whose table all layers share; it has
-    no rolling form either."""
+    no rolling form either.  "paged_mxfp8" is the same with
+    :class:`PagedMXKVCache` layers: MXFP8 rows inside the pages."""
     if kv_format not in KV_FORMATS:
         raise ValueError(f"kv_format {kv_format!r} not supported (one of "
                          f"{KV_FORMATS})")
-    if kv_format == "paged":
+    if kv_format in ("paged", "paged_mxfp8"):
         if window is not None and window < max_seq:
             raise NotImplementedError(
-                "kv_format='paged' with a sliding window smaller than "
-                "max_seq: the rolling cache has no paged form")
+                f"kv_format={kv_format!r} with a sliding window smaller "
+                f"than max_seq: the rolling cache has no paged form")
         if page_pool is None or page_pool.batch != batch:
-            raise ValueError(f"kv_format='paged' needs a page_pool for a "
-                             f"batch of {batch}")
-        return [PagedKVCache(page_pool, n_kv_heads_local, head_dim, dtype,
-                             device)
+            raise ValueError(f"kv_format={kv_format!r} needs a page_pool "
+                             f"for a batch of {batch}")
+        cls = PagedKVCache if kv_format == "paged" else PagedMXKVCache
+        return [cls(page_pool, n_kv_heads_local, head_dim, dtype, device)
                 for _ in range(n_layers)]
     if kv_format == "mxfp8":
         if window is not None and window < max_seq:
@@ -450,5 +451,105 @@ class PagedKVCache:
         for pages in (self.k_pages, self.v_pages):
             x = pages[idx].transpose(1, 2)   # (B, Hkv, pps, 16, D)
             x = torch.where(valid, x, 0)
+            out.append(x.reshape(B, x.shape[1], self.max_seq, x.shape[4]))
+        return tuple(out)
+
+
+class PagedMXKVCache(PagedKVCache):
+    """One layer's K/V in MXFP8 inside the pages of a :class:`PagePool`:
+    ``k_pages``, ``v_pages`` uint8 (num_pages, Hkv, PAGE_ROWS, D), the e4m3
+    payload, and ``k_scale_pages``, ``v_scale_pages`` uint8 (num_pages, Hkv,
+    PAGE_ROWS, D/32), biased e8m0.  A row's bytes are exactly
+    ``pack_mx(*quantize_mx(row, "fp8_e4m3"), "fp8_e4m3")``, the layout of
+    :class:`MXKVCache` row for row: 0.516 of the bf16 pools' bytes at
+    D = 128, on top of what paging saves.
+
+    Interface, activity rule and spare page are :class:`PagedKVCache`'s.  As
+    with :class:`MXKVCache` the cache is the single source of truth:
+    :meth:`gather`, and so what :meth:`update` returns for a tensor
+    position, are DEQUANTIZED copies in the compute ``dtype``, the rows just
+    written included.  Only the fused kernel (ops.paged_attn_mx_step) streams
+    the quantized bytes.
+
+    bf16 GPU tensors with D = 128 are stored by the native prefill kernel
+    (ops.paged_mx_kv_store); CPU tensors and other dtypes quantize through
+    quantization.microscaling and scatter, the reference."""
+
+    def __init__(self, pool: PagePool, n_kv_heads: int, head_dim: int,
+                 dtype=torch.bfloat16, device=None):
+        if head_dim < 32 or head_dim % 32 != 0:
+            raise ValueError(f"PagedMXKVCache: head_dim {head_dim} must be a "
+                             f"multiple of the MX block (32)")
+        self.pool = pool
+        device = device or pool.block_table.device
+        n = pool.num_pages
+        # the spare page of PagedKVCache, in all four pools
+        self._k = torch.zeros(n + 1, n_kv_heads, PAGE_ROWS, head_dim,
+                              dtype=torch.uint8, device=device)
+        self._v = torch.zeros_like(self._k)
+        self._ks = torch.zeros(n + 1, n_kv_heads, PAGE_ROWS, head_dim // 32,
+                               dtype=torch.uint8, device=device)
+        self._vs = torch.zeros_like(self._ks)
+        self.k_pages, self.v_pages = self._k[:n], self._v[:n]
+        self.k_scale_pages, self.v_scale_pages = self._ks[:n], self._vs[:n]
+        self.max_seq = PAGE_ROWS * pool.pages_per_seq
+        self.dtype = dtype
+
+    def _scatter(self, k_new, v_new, rows, ok) -> None:
+        """:meth:`PagedKVCache._scatter` of the quantized rows: payload and
+        scales go to the same (page, slot), skipped ones to the spare page."""
+        pps, n = self.pool.pages_per_seq, self.pool.num_pages
+        j = torch.div(rows, PAGE_ROWS, rounding_mode="floor")
+        ok = ok & (j >= 0) & (j < pps)
+        j = j.clamp(0, pps - 1)
+        ok = ok & self._valid().gather(1, j)
+        page = torch.where(ok, self.pool.block_table.gather(1, j).long(), n)
+        slot = rows % PAGE_ROWS
+        for new, pay, scl in ((k_new, self._k, self._ks),
+                              (v_new, self._v, self._vs)):
+            q, s = MXKVCache._quantize(new.permute(0, 2, 1, 3))
+            pay[page, :, slot] = q
+            scl[page, :, slot] = s
+
+    def update(self, k_new: torch.Tensor, v_new: torch.Tensor, pos,
+               chunk_lens=None):
+        """Signature and modes of :meth:`PagedKVCache.update`.  The int
+        ``pos`` = 0 prefill stores the quantized rows and returns
+        (k_new, v_new); a tensor ``pos`` returns :meth:`gather`, dequantized
+        copies of what the pages hold."""
+        if isinstance(pos, torch.Tensor) or chunk_lens is not None \
+                or pos != 0:
+            return super().update(k_new, v_new, pos, chunk_lens)
+        B, _, S, D = k_new.shape
+        if k_new.is_cuda and D == 128 and k_new.dtype == torch.bfloat16 \
+                and v_new.dtype == torch.bfloat16:
+            from .. import ops
+
+            ops.paged_mx_kv_store(k_new, v_new, self.k_pages,
+                                  self.k_scale_pages, self.v_pages,
+                                  self.v_scale_pages, self.pool.block_table,
+                                  0)
+        else:
+            rows = torch.arange(S, device=k_new.device).expand(B, S)
+            self._scatter(k_new, v_new, rows, rows >= 0)
+        return k_new, v_new
+
+    def gather(self):
+        """Dense (B, Hkv, 16 * pages_per_seq, D) DEQUANTIZED copies of K and
+        V in ``dtype`` built from the table; pages without a valid entry
+        read as zeros."""
+        from ..quantization.microscaling import dequantize_mx, unpack_mx
+
+        t = self.pool.block_table
+        B, pps = t.shape
+        valid = self._valid().view(B, 1, pps, 1, 1)
+        idx = t.clamp(0, self.pool.num_pages - 1).long()
+        out = []
+        for pay, scl in ((self.k_pages, self.k_scale_pages),
+                         (self.v_pages, self.v_scale_pages)):
+            # zero bytes dequantize to zero: 0 * 2^-127
+            p = torch.where(valid, pay[idx].transpose(1, 2), 0)
+            s = torch.where(valid, scl[idx].transpose(1, 2), 0)
+            x = dequantize_mx(*unpack_mx(p, s, "fp8_e4m3"), dtype=self.dtype)
             out.append(x.reshape(B, x.shape[1], self.max_seq, x.shape[4]))
         return tuple(out)

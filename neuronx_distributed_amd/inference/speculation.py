@@ -149,6 +149,10 @@ def speculative_generate(target, draft, input_ids: torch.Tensor,
     through ops.paged_chunk_attn_step."""
     if prompt_lens is not None and not per_sequence:
         raise ValueError("prompt_lens needs per_sequence=True")
+    if kv_format == "paged_mxfp8":
+        raise ValueError("kv_format='paged_mxfp8' has no speculative path: "
+                         "its multi-token steps are not fused; use 'paged' "
+                         "or 'mxfp8'")
     if kv_format == "paged" and not per_sequence:
         raise ValueError("kv_format='paged' needs per_sequence=True: a paged "
                          "cache keeps one position per sequence")

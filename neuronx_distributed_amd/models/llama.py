@@ -213,11 +213,11 @@ class LlamaAttention(nn.Module):
             # hipGraph-capturable decode: device-tensor position, S == 1
             # (or a chunk of 2..8 tokens: speculative verification),
             # full-cache masked attention (no dynamic shapes)
-            from ..inference.kv_cache import PagedKVCache
+            from ..inference.kv_cache import PagedKVCache, PagedMXKVCache
 
             # a longer chunk: chunked prefill, on a paged cache only
-            if not 1 <= S <= 8 and (S < 1
-                                    or type(kv_cache) is not PagedKVCache):
+            if not 1 <= S <= 8 and (S < 1 or type(kv_cache) not in (
+                    PagedKVCache, PagedMXKVCache)):
                 raise ValueError(
                     f"a device-tensor position takes 1..8 tokens per "
                     f"forward, got {S}; use an int position for a longer "
@@ -292,11 +292,19 @@ class LlamaAttention(nn.Module):
         Padding tokens store nothing and their outputs are zero, like those
         of an inactive sequence.  It goes through ops.paged_prefill_attn_step
         where ops.paged_prefill_attn_available() under the conditions above,
-        and through the torch chain otherwise."""
-        from ..inference.kv_cache import KVCache, MXKVCache, PagedKVCache
+        and through the torch chain otherwise.
+
+        A PagedMXKVCache (MXFP8 rows inside the pages) is paged in every
+        respect above.  S = 1 goes through ops.paged_attn_mx_step where
+        ops.paged_attn_mx_available(), under the same conditions; it has no
+        fused multi-token or prefill kernel yet, so S = 2..8 and S > 8 take
+        the torch chain on the dequantized kv_cache.gather()."""
+        from ..inference.kv_cache import (KVCache, MXKVCache, PagedKVCache,
+                                          PagedMXKVCache)
 
         B, S = q.shape[0], q.shape[1]
-        paged = type(kv_cache) is PagedKVCache
+        paged_mx = type(kv_cache) is PagedMXKVCache
+        paged = paged_mx or type(kv_cache) is PagedKVCache
         ragged = B > 1 and pos_t.numel() == B
         if not ragged and pos_t.numel() != 1:
             raise ValueError(
@@ -329,8 +337,22 @@ class LlamaAttention(nn.Module):
         fusable = (paged and q.is_cuda and self.head_dim == 128
                    and rep in (1, 2, 4, 8) and q.dtype == torch.bfloat16
                    and self.sliding_window is None
-                   and kv_cache.k_pages.dtype == torch.bfloat16
-                   and kv_cache.k_pages.is_cuda and ops.paged_attn_available())
+                   and kv_cache.k_pages.is_cuda)
+        if fusable and paged_mx:
+            fusable = S == 1 and ops.paged_attn_mx_available()
+        elif fusable:
+            fusable = (kv_cache.k_pages.dtype == torch.bfloat16
+                       and ops.paged_attn_available())
+        if fusable and paged_mx:
+            out = ops.paged_attn_mx_step(
+                _flat(q), _flat(k), _flat(v), kv_cache.k_pages,
+                kv_cache.k_scale_pages, kv_cache.v_pages,
+                kv_cache.v_scale_pages, kv_cache.pool.block_table, cos, sin,
+                pos_t.reshape(B).contiguous(), self.num_heads_local,
+                self.num_kv_local, scale).unsqueeze(1)  # (B, 1, H*D)
+            if sp:
+                out = out.transpose(0, 1)
+            return self.o_proj(out)
         if fusable and S > 8:
             fusable = ops.paged_prefill_attn_available()
         elif fusable and S > 1:

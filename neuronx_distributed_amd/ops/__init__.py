@@ -1874,3 +1874,137 @@ def paged_kv_store(k: torch.Tensor, v: torch.Tensor, k_pages: torch.Tensor,
         raise ValueError(f"paged_kv_store rejected k {tuple(k.shape)} strides "
                          f"{k.stride()} at pos0 {pos0}, pools "
                          f"{tuple(k_pages.shape)}")
+
+
+# ---------------------------------------------------------------------------
+# Paged MXFP8 KV cache: fused one-token decode attention + prefill store
+# (csrc/paged_attn_mx.hip)
+# ---------------------------------------------------------------------------
+
+def paged_attn_mx_available() -> bool:
+    lib = _load()
+    return (lib is not None and hasattr(lib, "paged_decode_attn_mx")
+            and hasattr(lib, "paged_mx_kv_store"))
+
+
+def _paged_mx_check_pools(who, k_pages, k_scale_pages, v_pages, v_scale_pages,
+                          block_table, B, Hkv):
+    """The four pools of a PagedMXKVCache, contiguous uint8 (num_pages, Hkv,
+    16, 128) payload and (num_pages, Hkv, 16, 4) scales on one GPU, and the
+    table, contiguous int32 (B, >= 1) beside them.  Returns (num_pages,
+    pages_per_seq)."""
+    n = k_pages.shape[0] if k_pages.dim() == 4 else -1
+    for name, t, w in (("k_pages", k_pages, _DA_D),
+                       ("k_scale_pages", k_scale_pages, _DA_D // 32),
+                       ("v_pages", v_pages, _DA_D),
+                       ("v_scale_pages", v_scale_pages, _DA_D // 32)):
+        # bf16 pools are twice as large, but their rows are no MX rows
+        if t.dtype != torch.uint8 or not t.is_cuda or n < 1 \
+                or t.device != k_pages.device \
+                or tuple(t.shape) != (n, Hkv, _PG_ROWS, w) \
+                or not t.is_contiguous():
+            raise ValueError(f"{who}: {name} must be a contiguous uint8 "
+                             f"(num_pages, {Hkv}, {_PG_ROWS}, {w}) pool on "
+                             f"the GPU of k_pages, got {t.dtype} "
+                             f"{tuple(t.shape)} strides {t.stride()} on "
+                             f"{t.device}")
+    t = block_table
+    if t.dtype != torch.int32 or t.device != k_pages.device or t.dim() != 2 \
+            or t.shape[0] != B or t.shape[1] < 1 or not t.is_contiguous():
+        raise ValueError(f"{who}: block_table must be a contiguous int32 "
+                         f"({B}, >= 1) tensor on {k_pages.device}, got "
+                         f"{t.dtype} {tuple(t.shape)} strides {t.stride()} "
+                         f"on {t.device}")
+    return n, t.shape[1]
+
+
+def paged_attn_mx_step(q2: torch.Tensor, k2: torch.Tensor, v2: torch.Tensor,
+                       k_pages: torch.Tensor, k_scale_pages: torch.Tensor,
+                       v_pages: torch.Tensor, v_scale_pages: torch.Tensor,
+                       block_table: torch.Tensor, cos: torch.Tensor,
+                       sin: torch.Tensor, pos_t: torch.Tensor, Hq: int,
+                       Hkv: int, scale: float) -> torch.Tensor:
+    """:func:`paged_attn_step` over MXFP8 pages (``PagedMXKVCache`` pools):
+    k_pages/v_pages uint8 (num_pages, Hkv, 16, 128), the e4m3 payload;
+    k_scale_pages/v_scale_pages uint8 (num_pages, Hkv, 16, 4), biased e8m0;
+    block_table, cos/sin and pos_t as there -> out (B, Hq*128).
+
+    Sequence b ropes its new row at ``pos_t[b]``, quantizes K and V and
+    appends them to slot ``pos_t[b] % 16`` of page
+    ``block_table[b, pos_t[b] // 16]`` in all four pools (the bytes equal
+    ``pack_mx(quantize_mx(row))``), and attends its rows [0, pos_t[b]] as
+    stored, the new row included.  Activity is :func:`paged_attn_step`'s
+    rule, checked by the kernel; rows at or beyond ``pos_t[b]`` are never
+    read, whatever bytes they hold.  Shapes and dtypes are validated here
+    without a device sync (hipGraph-capturable); a wrong one raises
+    ValueError and launches nothing."""
+    lib = _require_lib()
+    who = "paged_attn_mx_step"
+    if not paged_attn_mx_available():
+        raise RuntimeError("nxd_ops library has no paged_decode_attn_mx — "
+                           "rebuild")
+    B = q2.shape[0] if q2.dim() == 2 else -1
+    num_pages, pps = _paged_mx_check_pools(
+        who, k_pages, k_scale_pages, v_pages, v_scale_pages, block_table, B,
+        Hkv)
+    dev = k_pages.device
+    _, st = _decode_attn_check(who, False, q2, k2, v2, cos, sin, pos_t, B, Hq,
+                               Hkv, _PG_ROWS * pps, dev, ragged=True)
+    ws = _decode_attn_workspace(B, 1, Hq, Hkv, dev, False)
+    rc = lib.paged_decode_attn_mx(
+        *map(_ptr, (q2, k2, v2, k_pages, k_scale_pages, v_pages,
+                    v_scale_pages, block_table, cos, sin, pos_t) + ws),
+        B, Hq, Hkv, num_pages, pps, ctypes.c_float(scale), *st, _stream())
+    if rc != 0:
+        raise ValueError(f"paged_decode_attn_mx rejected B={B}, Hq={Hq}, "
+                         f"Hkv={Hkv}, num_pages={num_pages}, "
+                         f"pages_per_seq={pps}, strides {list(st)}")
+    return ws[2]
+
+
+def paged_mx_kv_store(k: torch.Tensor, v: torch.Tensor, k_pages: torch.Tensor,
+                      k_scale_pages: torch.Tensor, v_pages: torch.Tensor,
+                      v_scale_pages: torch.Tensor, block_table: torch.Tensor,
+                      pos0: int = 0) -> None:
+    """Quantize bf16 k, v (B, Hkv, S, 128) to MXFP8 straight into the pages
+    of rows [pos0, pos0 + S) of every sequence in one launch.  Views and
+    strides as :func:`paged_kv_store`, and its skip rule: a row beyond the
+    table, or whose table entry lies outside [0, num_pages), stores nothing.
+    Written bytes equal ``pack_mx(*quantize_mx(x, "fp8_e4m3"))``.  Contract
+    violations raise ValueError and launch nothing."""
+    lib = _require_lib()
+    who = "paged_mx_kv_store"
+    if not paged_attn_mx_available():
+        raise RuntimeError("nxd_ops library has no paged_mx_kv_store — "
+                           "rebuild")
+    if k.dim() != 4 or k.shape[2] < 1 or k.shape[3] != _DA_D \
+            or tuple(v.shape) != tuple(k.shape):
+        raise ValueError(f"{who}: k {tuple(k.shape)} / v {tuple(v.shape)} "
+                         f"must be one (B, Hkv, S >= 1, {_DA_D}) shape")
+    B, Hkv, S, _ = k.shape
+    num_pages, pps = _paged_mx_check_pools(
+        who, k_pages, k_scale_pages, v_pages, v_scale_pages, block_table, B,
+        Hkv)
+    dev = k_pages.device
+    pos0 = int(pos0)
+    if pos0 < 0:
+        raise ValueError(f"{who}: pos0 {pos0} is negative")
+    for name, t in (("k", k), ("v", v)):
+        if t.dtype != torch.bfloat16 or t.device != dev:
+            raise ValueError(f"{who}: {name} must be bf16 on {dev}, got "
+                             f"{t.dtype} on {t.device}")
+        if t.stride(3) != 1 or any(st < 0 or st % 8 for st in t.stride()[:3]) \
+                or t.data_ptr() % 16:
+            raise ValueError(f"{who}: {name} needs a dense last dim, strides "
+                             f"that are multiples of 8 and 16-byte "
+                             f"alignment, got strides {t.stride()}")
+    rc = lib.paged_mx_kv_store(
+        _ptr(k), _ptr(v), (ctypes.c_long * 4)(*k.stride()),
+        (ctypes.c_long * 4)(*v.stride()),
+        *map(_ptr, (k_pages, k_scale_pages, v_pages, v_scale_pages,
+                    block_table)),
+        B, Hkv, S, num_pages, pps, ctypes.c_long(pos0), _stream())
+    if rc != 0:
+        raise ValueError(f"paged_mx_kv_store rejected k {tuple(k.shape)} "
+                         f"strides {k.stride()} at pos0 {pos0}, pools "
+                         f"{tuple(k_pages.shape)}")

@@ -29,6 +29,7 @@ ARCH = os.environ.get("NXDA_GPU_ARCH", "gfx950")
 # it; tests/bench_paged_attn.py --dense-lib compares like with like.
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {"paged_attn.hip": _NO_PACKED_FP32,
+               "paged_attn_mx.hip": _NO_PACKED_FP32,
                "paged_chunk_attn.hip": _NO_PACKED_FP32,
                "paged_prefill_attn.hip": _NO_PACKED_FP32}
 

@@ -46,33 +46,7 @@
 #endif
 #define DAMX_RPI (DAMX_U * DA_SLOTS)              // rows per WG-iteration
 
-// One thread quantizes the 32-element block `blk` of a 128-wide bf16 row held
-// in LDS, writes payload + scale byte to the cache row and the dequantized
-// values back to LDS.
-__device__ __forceinline__ void damx_append_block(
-    const short* __restrict__ row_bits, int blk, uint8_t* __restrict__ payload,
-    uint8_t* __restrict__ scales, float* __restrict__ deq) {
-  s8v v[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[i][j] = row_bits[32 * blk + 8 * i + j];
-  uint4v out[2];
-  const int e = mxq_block32(v, out);
-  const float sc = mxq_scale((unsigned)(e + 127));
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    float f[8];
-    mxq_dcvt8(uint2v{out[i >> 1][2 * (i & 1)], out[i >> 1][2 * (i & 1) + 1]},
-              f);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) deq[32 * blk + 8 * i + j] = f[j] * sc;
-  }
-  uint4v* dst = (uint4v*)(payload + 32 * blk);
-  dst[0] = out[0];
-  dst[1] = out[1];
-  scales[blk] = (uint8_t)(e + 127);
-}
+#include "damx_append.h"  // damx_append_block, shared with paged_attn_mx.hip
 
 template <int REP, bool RAGGED>
 __global__ void __launch_bounds__(DA_WAVES * 64)

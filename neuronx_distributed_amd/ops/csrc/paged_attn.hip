@@ -29,23 +29,8 @@
 // nothing else.  Sequences may share pages for reading; two that append into
 // one slot in the same step leave that slot undefined.
 
-#include "decode_attn_common.h"
 #include "mfma.h"  // uint4v
-
-#define PG_ROWS DA_SLOTS
-#define PG_THREADS (DA_WAVES * 64)
-
-// a table entry that names a pool page
-__device__ __forceinline__ bool pg_valid(int e, int num_pages) {
-  return (unsigned)e < (unsigned)num_pages;
-}
-
-// The pool page of page p of a sequence (tab its table row), 0 at p >= p1.
-// Workgroup-uniform: one scalar load, the id stays in a scalar register.
-__device__ __forceinline__ int pg_id(const int* __restrict__ tab, int p,
-                                     int p1) {
-  return p < p1 ? __builtin_amdgcn_readfirstlane(tab[p]) : 0;
-}
+#include "paged_common.h"  // PG_ROWS, pg_valid, pg_id, PgKvSrc
 
 template <int REP>
 __global__ void __launch_bounds__(PG_THREADS)
@@ -218,11 +203,6 @@ extern "C" int paged_decode_attn(const void* qlin, const void* klin,
 // row.  Strides are in elements: (batch, head, seq); the last dim is dense.
 // A row beyond the table, or whose entry names no pool page, is skipped.
 // ---------------------------------------------------------------------------
-struct PgKvSrc {
-  const short* p;
-  long sb, sh, ss;
-};
-
 #define PG_PIECES (DA_D / 8)  // 16-byte pieces per row
 
 __global__ void __launch_bounds__(256)
