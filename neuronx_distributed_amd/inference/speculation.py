@@ -146,16 +146,15 @@ def speculative_generate(target, draft, input_ids: torch.Tensor,
     of sum_b ceil((len_b + max_new_tokens + spec_len + 1) / 16) pages,
     allocated up front.  On GPU the one-token draft steps then run through
     ops.paged_attn_step, the draft's two-token step and the verify chunk
-    through ops.paged_chunk_attn_step."""
+    through ops.paged_chunk_attn_step.  ``kv_format="paged_mxfp8"``: the same
+    rules and pools with MXFP8 rows inside the pages, through
+    ops.paged_attn_mx_step and ops.paged_chunk_attn_mx_step."""
     if prompt_lens is not None and not per_sequence:
         raise ValueError("prompt_lens needs per_sequence=True")
-    if kv_format == "paged_mxfp8":
-        raise ValueError("kv_format='paged_mxfp8' has no speculative path: "
-                         "its multi-token steps are not fused; use 'paged' "
-                         "or 'mxfp8'")
-    if kv_format == "paged" and not per_sequence:
-        raise ValueError("kv_format='paged' needs per_sequence=True: a paged "
-                         "cache keeps one position per sequence")
+    paged = kv_format in ("paged", "paged_mxfp8")
+    if paged and not per_sequence:
+        raise ValueError(f"kv_format={kv_format!r} needs per_sequence=True: "
+                         f"a paged cache keeps one position per sequence")
     B, S = input_ids.shape
     dev = input_ids.device
     extra = max_new_tokens + spec_len + 1   # rows beyond a prompt
@@ -168,7 +167,7 @@ def speculative_generate(target, draft, input_ids: torch.Tensor,
         kv_mult = max(1, tp // cfg.num_key_value_heads)
         n_kv_local = cfg.num_key_value_heads * kv_mult // tp
         pool = None
-        if kv_format == "paged":
+        if paged:
             # as generate(): every sequence allocated up front, so the table
             # is static; stale rows of a rejected chunk stay inside it
             from .generation import check_prompt_lens

@@ -295,10 +295,12 @@ class LlamaAttention(nn.Module):
         and through the torch chain otherwise.
 
         A PagedMXKVCache (MXFP8 rows inside the pages) is paged in every
-        respect above.  S = 1 goes through ops.paged_attn_mx_step where
-        ops.paged_attn_mx_available(), under the same conditions; it has no
-        fused multi-token or prefill kernel yet, so S = 2..8 and S > 8 take
-        the torch chain on the dequantized kv_cache.gather()."""
+        respect above.  Under the same conditions S = 1 goes through
+        ops.paged_attn_mx_step where ops.paged_attn_mx_available(), and
+        S = 2..8 through ops.paged_chunk_attn_mx_step where
+        ops.paged_chunk_attn_mx_available() as well; it has no fused prefill
+        kernel yet, so S > 8 takes the torch chain on the dequantized
+        kv_cache.gather()."""
         from ..inference.kv_cache import (KVCache, MXKVCache, PagedKVCache,
                                           PagedMXKVCache)
 
@@ -339,17 +341,25 @@ class LlamaAttention(nn.Module):
                    and self.sliding_window is None
                    and kv_cache.k_pages.is_cuda)
         if fusable and paged_mx:
-            fusable = S == 1 and ops.paged_attn_mx_available()
+            fusable = S <= 8 and ops.paged_attn_mx_available() and (
+                S == 1 or ops.paged_chunk_attn_mx_available())
         elif fusable:
             fusable = (kv_cache.k_pages.dtype == torch.bfloat16
                        and ops.paged_attn_available())
         if fusable and paged_mx:
-            out = ops.paged_attn_mx_step(
-                _flat(q), _flat(k), _flat(v), kv_cache.k_pages,
+            qf, kf, vf = _flat(q), _flat(k), _flat(v)
+            if S > 1 and kf.stride() != vf.stride():
+                kf, vf = kf.contiguous(), vf.contiguous()
+            step = ops.paged_attn_mx_step if S == 1 \
+                else ops.paged_chunk_attn_mx_step
+            out = step(
+                qf, kf, vf, kv_cache.k_pages,
                 kv_cache.k_scale_pages, kv_cache.v_pages,
                 kv_cache.v_scale_pages, kv_cache.pool.block_table, cos, sin,
                 pos_t.reshape(B).contiguous(), self.num_heads_local,
-                self.num_kv_local, scale).unsqueeze(1)  # (B, 1, H*D)
+                self.num_kv_local, scale)
+            if S == 1:
+                out = out.unsqueeze(1)  # (B, 1, H*D)
             if sp:
                 out = out.transpose(0, 1)
             return self.o_proj(out)

@@ -1878,7 +1878,8 @@ def paged_kv_store(k: torch.Tensor, v: torch.Tensor, k_pages: torch.Tensor,
 
 # ---------------------------------------------------------------------------
 # Paged MXFP8 KV cache: fused one-token decode attention + prefill store
-# (csrc/paged_attn_mx.hip)
+# (csrc/paged_attn_mx.hip) and the multi-token step (the MX form of
+# csrc/paged_chunk_attn.hip)
 # ---------------------------------------------------------------------------
 
 def paged_attn_mx_available() -> bool:
@@ -2008,3 +2009,54 @@ def paged_mx_kv_store(k: torch.Tensor, v: torch.Tensor, k_pages: torch.Tensor,
         raise ValueError(f"paged_mx_kv_store rejected k {tuple(k.shape)} "
                          f"strides {k.stride()} at pos0 {pos0}, pools "
                          f"{tuple(k_pages.shape)}")
+
+
+def paged_chunk_attn_mx_available() -> bool:
+    lib = _load()
+    return lib is not None and hasattr(lib, "paged_chunk_attn_mx")
+
+
+def paged_chunk_attn_mx_step(q3: torch.Tensor, k3: torch.Tensor,
+                             v3: torch.Tensor, k_pages: torch.Tensor,
+                             k_scale_pages: torch.Tensor,
+                             v_pages: torch.Tensor,
+                             v_scale_pages: torch.Tensor,
+                             block_table: torch.Tensor, cos: torch.Tensor,
+                             sin: torch.Tensor, pos_t: torch.Tensor, Hq: int,
+                             Hkv: int, scale: float) -> torch.Tensor:
+    """:func:`paged_chunk_attn_step` over MXFP8 pages (``PagedMXKVCache``
+    pools, as for :func:`paged_attn_mx_step`): T = 2..8 new tokens per
+    sequence -> out (B, T, Hq*128).
+
+    Token t of sequence b is roped at ``pos_t[b] + t``, K and V are quantized
+    and stored in slot ``(pos_t[b] + t) % 16`` of page
+    ``block_table[b, (pos_t[b] + t) // 16]`` of all four pools (the bytes
+    equal ``pack_mx(quantize_mx(row))``), and the token attends rows
+    [0, pos_t[b] + t] as stored, the new rows included.  Activity is
+    :func:`paged_chunk_attn_step`'s rule, checked by the kernel; rows at or
+    beyond ``pos_t[b] + T`` contribute nothing, whatever bytes they hold.  No
+    device sync (hipGraph-capturable); a wrong dtype or shape raises
+    ValueError and launches nothing."""
+    lib = _require_lib()
+    who = "paged_chunk_attn_mx_step"
+    if not paged_chunk_attn_mx_available():
+        raise RuntimeError("nxd_ops library has no paged_chunk_attn_mx — "
+                           "rebuild")
+    B = q3.shape[0] if q3.dim() == 3 else -1
+    num_pages, pps = _paged_mx_check_pools(
+        who, k_pages, k_scale_pages, v_pages, v_scale_pages, block_table, B,
+        Hkv)
+    dev = k_pages.device
+    T, st = _decode_attn_check(who, True, q3, k3, v3, cos, sin, pos_t, B, Hq,
+                               Hkv, _PG_ROWS * pps, dev, ragged=True)
+    ws = _decode_attn_workspace(B, T, Hq, Hkv, dev, True)
+    rc = lib.paged_chunk_attn_mx(
+        *map(_ptr, (q3, k3, v3, k_pages, k_scale_pages, v_pages,
+                    v_scale_pages, block_table, cos, sin, pos_t) + ws),
+        B, T, Hq, Hkv, num_pages, pps, ctypes.c_float(scale), *st, _stream())
+    if rc != 0:
+        raise ValueError(f"paged_chunk_attn_mx rejected B={B}, T={T}, "
+                         f"Hq={Hq}, Hkv={Hkv}, num_pages={num_pages}, "
+                         f"pages_per_seq={pps}, strides "
+                         f"{[s.value for s in st]}")
+    return ws[2]

@@ -139,8 +139,6 @@ chunk_attn_append(const short* __restrict__ kin, const short* __restrict__ vin,
 // ---------------------------------------------------------------------------
 // 2. phase 1.  Staging of one 32-row tile by one wave.
 // ---------------------------------------------------------------------------
-template <> struct CaRegs<true> { uint4v k[4], v[4]; unsigned ks[4], vs[4]; };
-
 // bf16: lane l, step i owns row 4i + (l >> 4), 16-byte chunk l & 15.
 // Rows >= n read row n - 1 and are zeroed.
 __device__ __forceinline__ void ca_load(CaRegs<false>& r, const void* kc,
@@ -176,34 +174,6 @@ __device__ __forceinline__ void ca_load(CaRegs<true>& r, const void* kc,
     const unsigned vs = *(const unsigned*)(vsc + ra * (DA_D / 32));
     r.ks[i] = ok ? ks : 0u;
     r.vs[i] = ok ? vs : 0u;
-  }
-}
-
-// 8 e4m3 bytes x scale -> 8 bf16 (exact: 4 significant bits, power-of-2 scale)
-__device__ __forceinline__ uint4v ca_deq8(unsigned w0, unsigned w1, float sc) {
-  float f[8];
-  mxq_dcvt8(uint2v{w0, w1}, f);
-  uint4v o;
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-    o[j] = pack_bf16x2(f[2 * j] * sc, f[2 * j + 1] * sc);
-  return o;
-}
-
-__device__ __forceinline__ void ca_write(const CaRegs<true>& r, char* kimg,
-                                         char* vimg, int lane) {
-  const int pc = lane & 7;
-  const int sh = 8 * (pc >> 1);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int row = 8 * i + (lane >> 3);
-    const float ksc = mxq_scale((r.ks[i] >> sh) & 0xff);
-    const float vsc = mxq_scale((r.vs[i] >> sh) & 0xff);
-    const int o0 = img_off(row, 2 * pc), o1 = img_off(row, 2 * pc + 1);
-    *(uint4v*)(kimg + o0) = ca_deq8(r.k[i][0], r.k[i][1], ksc);
-    *(uint4v*)(kimg + o1) = ca_deq8(r.k[i][2], r.k[i][3], ksc);
-    *(uint4v*)(vimg + o0) = ca_deq8(r.v[i][0], r.v[i][1], vsc);
-    *(uint4v*)(vimg + o1) = ca_deq8(r.v[i][2], r.v[i][3], vsc);
   }
 }
 

@@ -1,12 +1,14 @@
 // What the multi-token decode-attention kernels share: chunk_attn.hip (dense
-// bf16 and MXFP8 caches) and paged_chunk_attn.hip (bf16 page pool).  The
-// per-wave staging of a 32-row tile as the dual-use LDS image of mfma.h, the
-// RoPE of a query fragment and the launch contract.  Each file keeps its own
-// walk over the cache (ca_load there, pc_load here) and its own kernels.
+// bf16 and MXFP8 caches) and paged_chunk_attn.hip (bf16 and MXFP8 page
+// pools).  The per-wave staging of a 32-row tile as the dual-use LDS image of
+// mfma.h, with the dequantizing form for MXFP8 rows, the RoPE of a query
+// fragment and the launch contract.  Each file keeps its own walk over the
+// cache (ca_load there, pc_load here) and its own kernels.
 #pragma once
 
 #include "decode_attn_common.h"
 #include "flash_common.h"
+#include "mx_quant.h"
 
 #define CA_TMIN 2
 #define CA_TMAX 8
@@ -26,9 +28,11 @@ __device__ __forceinline__ void ca_wave_sync() {
 
 // The registers of one wave's share of a 32-row tile between its global loads
 // and its LDS writes.  bf16: lane l, step i owns row 4i + (l >> 4), 16-byte
-// chunk l & 15.
+// chunk l & 15.  MXFP8: step i owns row 8i + (l >> 3), payload bytes
+// 16 (l & 7) ..+15, and the row's four scale bytes as one dword.
 template <bool MX> struct CaRegs;
 template <> struct CaRegs<false> { uint4v k[8], v[8]; };
+template <> struct CaRegs<true> { uint4v k[4], v[4]; unsigned ks[4], vs[4]; };
 
 __device__ __forceinline__ uint4v ca_sel(bool ok, uint4v x) {
   const uint4v z = {0, 0, 0, 0};
@@ -42,6 +46,34 @@ __device__ __forceinline__ void ca_write(const CaRegs<false>& r, char* kimg,
     const int off = img_off(4 * i + (lane >> 4), lane & 15);
     *(uint4v*)(kimg + off) = r.k[i];
     *(uint4v*)(vimg + off) = r.v[i];
+  }
+}
+
+// 8 e4m3 bytes x scale -> 8 bf16 (exact: 4 significant bits, power-of-2 scale)
+__device__ __forceinline__ uint4v ca_deq8(unsigned w0, unsigned w1, float sc) {
+  float f[8];
+  mxq_dcvt8(uint2v{w0, w1}, f);
+  uint4v o;
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    o[j] = pack_bf16x2(f[2 * j] * sc, f[2 * j + 1] * sc);
+  return o;
+}
+
+__device__ __forceinline__ void ca_write(const CaRegs<true>& r, char* kimg,
+                                         char* vimg, int lane) {
+  const int pc = lane & 7;
+  const int sh = 8 * (pc >> 1);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int row = 8 * i + (lane >> 3);
+    const float ksc = mxq_scale((r.ks[i] >> sh) & 0xff);
+    const float vsc = mxq_scale((r.vs[i] >> sh) & 0xff);
+    const int o0 = img_off(row, 2 * pc), o1 = img_off(row, 2 * pc + 1);
+    *(uint4v*)(kimg + o0) = ca_deq8(r.k[i][0], r.k[i][1], ksc);
+    *(uint4v*)(kimg + o1) = ca_deq8(r.k[i][2], r.k[i][3], ksc);
+    *(uint4v*)(vimg + o0) = ca_deq8(r.v[i][0], r.v[i][1], vsc);
+    *(uint4v*)(vimg + o1) = ca_deq8(r.v[i][2], r.v[i][3], vsc);
   }
 }
 

@@ -10,6 +10,9 @@
 //                      paged_decode_attn_mx_part dequant of page rows
 //   chunk_attn.hip     chunk_attn_append         one thread per 32-block
 //                      chunk_attn_part           dequant of a tile into LDS
+//   paged_chunk_attn.hip  the MX forms of paged_chunk_append (one thread per
+//                      32-block) and paged_chunk_part (the same dequant, in
+//                      chunk_attn_common.h)
 //   mx_skinny.hip      the fused quantizer: one lane per 16-element half
 //                      block, in the MFMA's operand layout
 //

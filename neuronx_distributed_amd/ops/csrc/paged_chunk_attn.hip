@@ -5,13 +5,21 @@
 // sibling of chunk_attn_ragged (chunk_attn.hip): the verify forward of
 // per-sequence speculative decoding and chunked prefill on pages.
 //
+//   paged_chunk_attn    : bf16 pools (PagedKVCache)
+//   paged_chunk_attn_mx : MXFP8 pools (PagedMXKVCache: e4m3 payload pages
+//                         (num_pages, Hkv, 16, 128) + e8m0 scale pages
+//                         (num_pages, Hkv, 16, 4), both uint8); the MX = true
+//                         forms of the two kernels below
+//
 // Token t of sequence b is roped at pos[b] + t, its K/V row goes to slot
 // (pos[b] + t) % 16 of page table[b, (pos[b] + t) / 16], and it attends rows
 // [0, pos[b] + t] of its sequence as stored.  Three launches on one stream,
 // no atomics, no host sync:
 //
 //   1. paged_chunk_append: block (b, kvh, t).  RoPE of the new K row, then K
-//      and V into their page slot, with chunk_attn_append's arithmetic.
+//      and V into their page slot, with chunk_attn_append's arithmetic (MX:
+//      quantized by mx_quant.h to pack_mx(quantize_mx(row)), eight threads,
+//      one per 32-block, into the slot of all four pools).
 //   2. paged_chunk_part: workgroup (b, kvh, split), four waves.  The matrix
 //      work is chunk_attn_part's: the R = rep * T query rows of a KV head
 //      are the N side of 32x32x16 bf16 MFMA tiles (one or two 32-row
@@ -51,7 +59,38 @@
 // n = pos + T inside the last tile are ZEROED while staging (a masked P of 0
 // times a NaN V would still be NaN in an MFMA, chunk_attn.hip).
 //
+// MXFP8 pages.  The dequantizing stage of chunk_attn.hip (CaRegs<true>,
+// ca_write: e4m3 x e8m0 is exact in bf16) in front of the same LDS image, so
+// MFMAs, softmax and merge are the bf16 kernel's own text.  The walk keeps
+// its property with the MX staging map (step i of 4: row 8i + (lane >> 3),
+// payload bytes 16 (lane & 7) ..+15, the row's four scale bytes as one
+// aligned dword): steps 0..1 lie wholly in the first page and steps 2..3 in
+// the second, so again the seam falls between two load instructions and the
+// page of a step is a compile-time choice between the two scalar ids.  A
+// lane keeps two offsets, computed once: (kvh * 16 + (lane >> 3)) * 128 +
+// 16 (lane & 7) bytes into a payload page and (kvh * 16 + (lane >> 3)) * 4
+// into a scale page; step i adds 8 (i & 1) rows to both.  The eight lanes of
+// a row read the same scale dword, which the hardware serves as one request.
+// Stale rows (at or beyond n) may hold 0xFF, the NaN encodings of e4m3 and
+// e8m0: payload and scale word are zeroed by SELECT (never by a product)
+// before mxq_scale or the conversion sees them.  A tile is 32 x 132 bytes
+// per operand instead of 32 x 256, in 4 + 4 loads per lane instead of 8.
+//
+// Resource usage (gfx950, no packed fp32), REP 1 / 2 / 4 / 8 with one query
+// block, then REP 8 with two; no instantiation has scratch or spills:
+//   bf16: 256 VGPRs, 69 / 70 / 70 / 70 SGPRs, 2 waves per SIMD;
+//         256 VGPRs + 232 AGPRs, 50 SGPRs, 1 wave per SIMD
+//   MX:   238 VGPRs, 75 / 76 / 76 / 76 SGPRs, 2 waves per SIMD;
+//         256 VGPRs + 228 AGPRs, 56 SGPRs, 1 wave per SIMD
+// LDS 65792 bytes everywhere.  The bf16 numbers are those of the file before
+// it carried the MX forms, and the instruction stream of their tile loop is
+// unchanged; the scale pools are the LAST kernel arguments so that the
+// kernarg offsets of everything else stay as they were.
+//
 // Rejected:
+//   * a separate paged_chunk_attn_mx.hip: a third copy of the tile loop and
+//     the wave merge for a kernel that differs only in how a tile's rows
+//     reach the LDS image;
 //   * gathering the pages into a dense buffer and running chunk_attn_ragged:
 //     what the torch chain does, a second pass over every row per layer and
 //     step, and a buffer of max_seq rows per sequence that the pool exists
@@ -79,7 +118,7 @@
 //
 // Layouts: q (B, T, Hq*128), k/v (B, T, Hkv*128) bf16 pre-RoPE with element
 // strides (batch, token) and a dense last dim; k_pages / v_pages bf16
-// (num_pages, Hkv, 16, 128) contiguous; block_table int32 (B, pages_per_seq)
+// (num_pages, Hkv, 16, 128) contiguous (MX: as above); block_table int32 (B, pages_per_seq)
 // contiguous; cos/sin (>= 16 * pages_per_seq, 64) fp32; pos_ptr B device
 // int64; workspace as in chunk_attn.hip.
 
@@ -87,6 +126,7 @@
 
 #define PC_ROWS 16                    // rows of a page (PG_ROWS, paged_attn.hip)
 #define PC_THREADS (DA_WAVES * 64)
+#define PC_SC (DA_D / 32)             // scale bytes of an MXFP8 row
 static_assert(CA_TILE == 2 * PC_ROWS, "a tile is two pages");
 
 // Whether sequence b takes part (file header).  The whole workgroup calls it
@@ -109,14 +149,16 @@ __device__ __forceinline__ bool pc_active(const long* __restrict__ pos_ptr,
 // ---------------------------------------------------------------------------
 // 1. append: block (b, kvh, t), 128 threads
 // ---------------------------------------------------------------------------
+template <bool MX>
 __global__ void __launch_bounds__(128)
 paged_chunk_append(const short* __restrict__ kin, const short* __restrict__ vin,
-                   short* __restrict__ kpages, short* __restrict__ vpages,
+                   void* __restrict__ kpages, void* __restrict__ vpages,
                    const int* __restrict__ block_table,
                    const float* __restrict__ cosp,
                    const float* __restrict__ sinp,
                    const long* __restrict__ pos_ptr, int T, int Hkv,
-                   int num_pages, int pages_per_seq, long kv_bs, long kv_ts) {
+                   int num_pages, int pages_per_seq, long kv_bs, long kv_ts,
+                   uint8_t* __restrict__ ksc, uint8_t* __restrict__ vsc) {
   const int tok = blockIdx.x % T;
   const int pair = blockIdx.x / T;
   const int kvh = pair % Hkv;
@@ -143,10 +185,24 @@ paged_chunk_append(const short* __restrict__ kin, const short* __restrict__ vin,
     rows[1][i + 64] = vin[src + i + 64];
   }
   __syncthreads();
-  short* out = (tid < 64 ? kpages : vpages) + dst * DA_D;
-  const short* in = rows[tid >> 6];
-  const int i = tid & 63;
-  *(uint*)(out + 2 * i) = *(const uint*)(in + 2 * i);
+  if (!MX) {
+    short* out = (short*)(tid < 64 ? kpages : vpages) + dst * DA_D;
+    const short* in = rows[tid >> 6];
+    const int i = tid & 63;
+    *(uint*)(out + 2 * i) = *(const uint*)(in + 2 * i);
+  } else if (tid < 8) {  // one thread per 32-block: 4 of K, 4 of V
+    const int blk = tid & 3;
+    const s8v* in = (const s8v*)(rows[tid >> 2] + 32 * blk);
+    s8v v[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) v[i] = in[i];
+    uint4v out[2];
+    const int e = mxq_block32(v, out);
+    uint8_t* pay = (uint8_t*)(tid < 4 ? kpages : vpages) + dst * DA_D + 32 * blk;
+    ((uint4v*)pay)[0] = out[0];
+    ((uint4v*)pay)[1] = out[1];
+    (tid < 4 ? ksc : vsc)[dst * PC_SC + blk] = (uint8_t)(e + 127);
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -170,38 +226,93 @@ __device__ __forceinline__ PcIds pc_ids(const int* __restrict__ tab, int t,
   return id;
 }
 
-// Lane l, step i owns row 4i + (l >> 4) of the tile, 16-byte chunk l & 15:
-// steps 0..3 are the first page, steps 4..7 the second.  lane_off: this
-// lane's element offset inside a page (head, slot l >> 4, chunk).  Rows >= n
+// What a lane adds to a page id to reach its share of a page, computed once
+// per kernel.  bf16: the elements of a page and the lane's element offset
+// inside one (head, slot l >> 4, chunk l & 15).  MXFP8: the bytes of a page
+// in a payload pool and in a scale pool, and the lane's byte offsets inside
+// them (head, slot l >> 3; payload chunk l & 7, the slot's scale dword).
+template <bool MX> struct PcLane;
+template <> struct PcLane<false> { long page_elems, lane_off; };
+template <> struct PcLane<true> { long page_pay, page_sc, pay_off, sc_off; };
+
+__device__ __forceinline__ void pc_lane(PcLane<false>& a, int Hkv, int kvh,
+                                        int lane) {
+  a.page_elems = (long)Hkv * PC_ROWS * DA_D;
+  a.lane_off = ((long)kvh * PC_ROWS + (lane >> 4)) * DA_D + 8 * (lane & 15);
+}
+
+__device__ __forceinline__ void pc_lane(PcLane<true>& a, int Hkv, int kvh,
+                                        int lane) {
+  a.page_pay = (long)Hkv * PC_ROWS * DA_D;
+  a.page_sc = (long)Hkv * PC_ROWS * PC_SC;
+  a.pay_off = ((long)kvh * PC_ROWS + (lane >> 3)) * DA_D + 16 * (lane & 7);
+  a.sc_off = ((long)kvh * PC_ROWS + (lane >> 3)) * PC_SC;
+}
+
+// bf16: lane l, step i owns row 4i + (l >> 4) of the tile, 16-byte chunk
+// l & 15: steps 0..3 are the first page, steps 4..7 the second.  Rows >= n
 // are zeroed; their address stays inside the (valid) page of their step.
 __device__ __forceinline__ void pc_load(CaRegs<false>& r,
-                                        const short* __restrict__ kpages,
-                                        const short* __restrict__ vpages,
-                                        PcIds id, long page_elems,
-                                        long lane_off, int row0, int n,
-                                        int lane) {
+                                        const void* __restrict__ kpages,
+                                        const uint8_t*,
+                                        const void* __restrict__ vpages,
+                                        const uint8_t*, PcIds id,
+                                        const PcLane<false>& a, int row0,
+                                        int n, int lane) {
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
     const bool ok = row0 + 4 * i + (lane >> 4) < n;
-    const long off = (long)(i < 4 ? id.p0 : id.p1) * page_elems + lane_off +
-                     4 * (i & 3) * DA_D;
-    r.k[i] = ca_sel(ok, *(const uint4v*)(kpages + off));
-    r.v[i] = ca_sel(ok, *(const uint4v*)(vpages + off));
+    const long off = (long)(i < 4 ? id.p0 : id.p1) * a.page_elems +
+                     a.lane_off + 4 * (i & 3) * DA_D;
+    r.k[i] = ca_sel(ok, *(const uint4v*)((const short*)kpages + off));
+    r.v[i] = ca_sel(ok, *(const uint4v*)((const short*)vpages + off));
+  }
+}
+
+// MXFP8: lane l, step i owns row 8i + (l >> 3) of the tile, payload bytes
+// 16 (l & 7) ..+15 and the row's scale dword (ca_write picks the byte of the
+// lane's 32-block): steps 0..1 are the first page, steps 2..3 the second,
+// slots (l >> 3) and 8 + (l >> 3) of each.  Eight lanes read one scale
+// dword: one request, merged by the hardware.  Rows >= n may hold the NaN
+// bytes of e4m3 and e8m0: payload AND scale word are zeroed by select before
+// anything converts them; their addresses stay inside the (valid) page of
+// their step.
+__device__ __forceinline__ void pc_load(CaRegs<true>& r,
+                                        const void* __restrict__ kpages,
+                                        const uint8_t* __restrict__ ksc,
+                                        const void* __restrict__ vpages,
+                                        const uint8_t* __restrict__ vsc,
+                                        PcIds id, const PcLane<true>& a,
+                                        int row0, int n, int lane) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const bool ok = row0 + 8 * i + (lane >> 3) < n;
+    const long pg = i < 2 ? id.p0 : id.p1;
+    const long off = pg * a.page_pay + a.pay_off + 8 * (i & 1) * DA_D;
+    const long soff = pg * a.page_sc + a.sc_off + 8 * (i & 1) * PC_SC;
+    r.k[i] = ca_sel(ok, *(const uint4v*)((const uint8_t*)kpages + off));
+    r.v[i] = ca_sel(ok, *(const uint4v*)((const uint8_t*)vpages + off));
+    const unsigned ks = *(const unsigned*)(ksc + soff);
+    const unsigned vs = *(const unsigned*)(vsc + soff);
+    r.ks[i] = ok ? ks : 0u;
+    r.vs[i] = ok ? vs : 0u;
   }
 }
 
 // Second launch bound as for chunk_attn_part: two workgroups per CU with one
 // query block, one with two.
-template <int REP, int NQB>
+template <int REP, int NQB, bool MX>
 __global__ void __launch_bounds__(PC_THREADS, NQB == 1 ? 2 : 1)
 paged_chunk_part(const short* __restrict__ qin,
-                 const short* __restrict__ kpages,
-                 const short* __restrict__ vpages,
+                 const void* __restrict__ kpages,
+                 const void* __restrict__ vpages,
                  const int* __restrict__ block_table,
                  const float* __restrict__ cosp, const float* __restrict__ sinp,
                  const long* __restrict__ pos_ptr, float* __restrict__ part_o,
                  float* __restrict__ part_ml, int T, int Hkv, int num_pages,
-                 int pages_per_seq, float scale, long q_bs, long q_ts) {
+                 int pages_per_seq, float scale, long q_bs, long q_ts,
+                 const uint8_t* __restrict__ ksc,
+                 const uint8_t* __restrict__ vsc) {
   __shared__ __attribute__((aligned(16))) char smem[CA_LDS_B];
 
   const int wg = blockIdx.x;
@@ -229,9 +340,8 @@ paged_chunk_part(const short* __restrict__ qin,
   const int t0 = s * tchunk;
   const int t1 = min(ntiles, t0 + tchunk);
   const int* tab = block_table + (long)b * pages_per_seq;
-  const long page_elems = (long)Hkv * PC_ROWS * DA_D;
-  const long lane_off =
-      ((long)kvh * PC_ROWS + (lane >> 4)) * DA_D + 8 * (lane & 15);
+  PcLane<MX> la;
+  pc_lane(la, Hkv, kvh, lane);
 
   // ---- Q fragments, RoPE'd once: qf[qb][c] = Q[32qb + col][16c + 8hi + j]
   frag_u qf[NQB][8];
@@ -277,12 +387,12 @@ paged_chunk_part(const short* __restrict__ qin,
   // every branch below is on wave-uniform values (wid, pos and kernel
   // arguments): the transposed reads run with all 64 lanes active
   int t = t0 + wid;
-  CaRegs<false> regs;
+  CaRegs<MX> regs;
   // the ids of the tile whose rows the loop loads next: one tile ahead
   PcIds ahead = pc_ids(tab, t + DA_WAVES, t1, last);
   if (t < t1) {
-    pc_load(regs, kpages, vpages, pc_ids(tab, t, t1, last), page_elems,
-            lane_off, CA_TILE * t, n, lane);
+    pc_load(regs, kpages, ksc, vpages, vsc, pc_ids(tab, t, t1, last), la,
+            CA_TILE * t, n, lane);
     ca_write(regs, kimg, vimg, lane);
   }
   ca_wave_sync();
@@ -291,7 +401,7 @@ paged_chunk_part(const short* __restrict__ qin,
     // lands while the rows of tile t + DA_WAVES load
     const PcIds ahead2 = pc_ids(tab, t + 2 * DA_WAVES, t1, last);
     if (more)
-      pc_load(regs, kpages, vpages, ahead, page_elems, lane_off,
+      pc_load(regs, kpages, ksc, vpages, vsc, ahead, la,
               CA_TILE * (t + DA_WAVES), n, lane);
     ahead = ahead2;
 
@@ -422,7 +532,48 @@ paged_chunk_part(const short* __restrict__ qin,
 // q_bs/q_ts, kv_bs/kv_ts: element strides (batch, token) of q and of k = v.
 // Returns non-zero, launching nothing, outside ca_launch_ok's contract (with
 // Smax = 16 * pages_per_seq), with num_pages < 1 or pages_per_seq < 1, or
-// with pools or a table that break the aligned loads.
+// with pools or a table that break the aligned loads: 16 bytes for the bf16
+// and the payload pools, 4 for the scale pools (a row's scales are one
+// dword).
+template <bool MX>
+static int pc_launch(const void* q, const void* k, const void* v, void* kpages,
+                     void* ksc, void* vpages, void* vsc,
+                     const void* block_table, const void* cosp,
+                     const void* sinp, const void* pos_ptr, void* part_o,
+                     void* part_ml, void* outp, int B, int T, int Hq, int Hkv,
+                     int num_pages, int pages_per_seq, float scale, long q_bs,
+                     long q_ts, long kv_bs, long kv_ts, hipStream_t stream) {
+  if (num_pages < 1 || pages_per_seq < 1 ||
+      pages_per_seq > 0x7FFFFFFF / PC_ROWS)
+    return 1;
+  if (!ca_launch_ok(q, k, v, cosp, sinp, B, T, Hq, Hkv,
+                    PC_ROWS * pages_per_seq, q_bs, q_ts, kv_bs, kv_ts))
+    return 1;
+  if (((uintptr_t)kpages | (uintptr_t)vpages) % 16 ||
+      (MX && ((uintptr_t)ksc | (uintptr_t)vsc) % 4) ||
+      (uintptr_t)block_table % 4 || (uintptr_t)pos_ptr % 8)
+    return 1;
+  paged_chunk_append<MX><<<B * Hkv * T, 128, 0, stream>>>(
+      (const short*)k, (const short*)v, kpages, vpages,
+      (const int*)block_table, (const float*)cosp, (const float*)sinp,
+      (const long*)pos_ptr, T, Hkv, num_pages, pages_per_seq, kv_bs, kv_ts,
+      (uint8_t*)ksc, (uint8_t*)vsc);
+  da_for_rep(Hq / Hkv, [&](auto rep) {
+    constexpr int R = decltype(rep)::value;
+    // two query blocks: rep 8 only
+    auto part = paged_chunk_part<R, 1, MX>;
+    if constexpr (R == 8)
+      if (R * T > 32) part = paged_chunk_part<R, 2, MX>;
+    part<<<B * Hkv * DA_SPLIT, PC_THREADS, 0, stream>>>(
+        (const short*)q, kpages, vpages, (const int*)block_table,
+        (const float*)cosp, (const float*)sinp, (const long*)pos_ptr,
+        (float*)part_o, (float*)part_ml, T, Hkv, num_pages, pages_per_seq,
+        scale, q_bs, q_ts, (const uint8_t*)ksc, (const uint8_t*)vsc);
+  });
+  return decode_attn_merge_launch(part_o, part_ml, outp, B, T, Hq, Hkv,
+                                  stream);
+}
+
 extern "C" int paged_chunk_attn(const void* q, const void* k, const void* v,
                                 void* kpages, void* vpages,
                                 const void* block_table, const void* cosp,
@@ -432,31 +583,27 @@ extern "C" int paged_chunk_attn(const void* q, const void* k, const void* v,
                                 int pages_per_seq, float scale, long q_bs,
                                 long q_ts, long kv_bs, long kv_ts,
                                 hipStream_t stream) {
-  if (num_pages < 1 || pages_per_seq < 1 ||
-      pages_per_seq > 0x7FFFFFFF / PC_ROWS)
-    return 1;
-  if (!ca_launch_ok(q, k, v, cosp, sinp, B, T, Hq, Hkv,
-                    PC_ROWS * pages_per_seq, q_bs, q_ts, kv_bs, kv_ts))
-    return 1;
-  if (((uintptr_t)kpages | (uintptr_t)vpages) % 16 ||
-      (uintptr_t)block_table % 4 || (uintptr_t)pos_ptr % 8)
-    return 1;
-  paged_chunk_append<<<B * Hkv * T, 128, 0, stream>>>(
-      (const short*)k, (const short*)v, (short*)kpages, (short*)vpages,
-      (const int*)block_table, (const float*)cosp, (const float*)sinp,
-      (const long*)pos_ptr, T, Hkv, num_pages, pages_per_seq, kv_bs, kv_ts);
-  da_for_rep(Hq / Hkv, [&](auto rep) {
-    constexpr int R = decltype(rep)::value;
-    // two query blocks: rep 8 only
-    auto part = paged_chunk_part<R, 1>;
-    if constexpr (R == 8)
-      if (R * T > 32) part = paged_chunk_part<R, 2>;
-    part<<<B * Hkv * DA_SPLIT, PC_THREADS, 0, stream>>>(
-        (const short*)q, (const short*)kpages, (const short*)vpages,
-        (const int*)block_table, (const float*)cosp, (const float*)sinp,
-        (const long*)pos_ptr, (float*)part_o, (float*)part_ml, T, Hkv,
-        num_pages, pages_per_seq, scale, q_bs, q_ts);
-  });
-  return decode_attn_merge_launch(part_o, part_ml, outp, B, T, Hq, Hkv,
-                                  stream);
+  return pc_launch<false>(q, k, v, kpages, nullptr, vpages, nullptr,
+                          block_table, cosp, sinp, pos_ptr, part_o, part_ml,
+                          outp, B, T, Hq, Hkv, num_pages, pages_per_seq, scale,
+                          q_bs, q_ts, kv_bs, kv_ts, stream);
+}
+
+// The same over MXFP8 pages: kpay / vpay uint8 (num_pages, Hkv, 16, 128), ksc
+// / vsc uint8 (num_pages, Hkv, 16, 4).
+extern "C" int paged_chunk_attn_mx(const void* q, const void* k,
+                                   const void* v, void* kpay, void* ksc,
+                                   void* vpay, void* vsc,
+                                   const void* block_table, const void* cosp,
+                                   const void* sinp, const void* pos_ptr,
+                                   void* part_o, void* part_ml, void* outp,
+                                   int B, int T, int Hq, int Hkv,
+                                   int num_pages, int pages_per_seq,
+                                   float scale, long q_bs, long q_ts,
+                                   long kv_bs, long kv_ts,
+                                   hipStream_t stream) {
+  return pc_launch<true>(q, k, v, kpay, ksc, vpay, vsc, block_table, cosp,
+                         sinp, pos_ptr, part_o, part_ml, outp, B, T, Hq, Hkv,
+                         num_pages, pages_per_seq, scale, q_bs, q_ts, kv_bs,
+                         kv_ts, stream);
 }
