@@ -39,7 +39,8 @@ def main():
                         "pool")
     p.add_argument("--prefill-chunk", type=int, default=None,
                    help="with a paged --kv-format: prefill the prompt in "
-                        "chunks of this many tokens (more than 8)")
+                        "chunks of this many tokens (more than 8) through "
+                        "the fused paged prefill kernel of the format")
     args = p.parse_args()
 
     os.environ.setdefault("MASTER_ADDR", "127.0.0.1")

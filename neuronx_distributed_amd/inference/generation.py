@@ -171,7 +171,8 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int = 32,
     prompt in chunks of N tokens through the paged prefill kernel
     (ops.paged_prefill_attn_step), which bounds the activation memory of a
     long prompt; None is one prefill of the whole prompt.  On
-    ``"paged_mxfp8"`` the chunks run on the reference path."""
+    ``"paged_mxfp8"`` the chunks go through its MX form
+    (ops.paged_prefill_attn_mx_step)."""
     from ..parallel import parallel_state as ps
     from .decode_graph import GraphDecoder
 

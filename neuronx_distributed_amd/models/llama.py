@@ -298,9 +298,10 @@ class LlamaAttention(nn.Module):
         respect above.  Under the same conditions S = 1 goes through
         ops.paged_attn_mx_step where ops.paged_attn_mx_available(), and
         S = 2..8 through ops.paged_chunk_attn_mx_step where
-        ops.paged_chunk_attn_mx_available() as well; it has no fused prefill
-        kernel yet, so S > 8 takes the torch chain on the dequantized
-        kv_cache.gather()."""
+        ops.paged_chunk_attn_mx_available() as well, and S > 8 (with
+        ``chunk_lens`` as above) through ops.paged_prefill_attn_mx_step where
+        ops.paged_prefill_attn_mx_available() as well; everything else takes
+        the torch chain on the dequantized kv_cache.gather()."""
         from ..inference.kv_cache import (KVCache, MXKVCache, PagedKVCache,
                                           PagedMXKVCache)
 
@@ -341,8 +342,9 @@ class LlamaAttention(nn.Module):
                    and self.sliding_window is None
                    and kv_cache.k_pages.is_cuda)
         if fusable and paged_mx:
-            fusable = S <= 8 and ops.paged_attn_mx_available() and (
-                S == 1 or ops.paged_chunk_attn_mx_available())
+            fusable = ops.paged_attn_mx_available() and (
+                S == 1 or ops.paged_chunk_attn_mx_available()) and (
+                S <= 8 or ops.paged_prefill_attn_mx_available())
         elif fusable:
             fusable = (kv_cache.k_pages.dtype == torch.bfloat16
                        and ops.paged_attn_available())
@@ -352,12 +354,17 @@ class LlamaAttention(nn.Module):
                 kf, vf = kf.contiguous(), vf.contiguous()
             step = ops.paged_attn_mx_step if S == 1 \
                 else ops.paged_chunk_attn_mx_step
+            more = ()
+            if S > 8:
+                step = ops.paged_prefill_attn_mx_step
+                more = (None if chunk_lens is None
+                        else chunk_lens.reshape(B).contiguous(),)
             out = step(
                 qf, kf, vf, kv_cache.k_pages,
                 kv_cache.k_scale_pages, kv_cache.v_pages,
                 kv_cache.v_scale_pages, kv_cache.pool.block_table, cos, sin,
                 pos_t.reshape(B).contiguous(), self.num_heads_local,
-                self.num_kv_local, scale)
+                self.num_kv_local, scale, *more)
             if S == 1:
                 out = out.unsqueeze(1)  # (B, 1, H*D)
             if sp:

@@ -1878,8 +1878,9 @@ def paged_kv_store(k: torch.Tensor, v: torch.Tensor, k_pages: torch.Tensor,
 
 # ---------------------------------------------------------------------------
 # Paged MXFP8 KV cache: fused one-token decode attention + prefill store
-# (csrc/paged_attn_mx.hip) and the multi-token step (the MX form of
-# csrc/paged_chunk_attn.hip)
+# (csrc/paged_attn_mx.hip), the multi-token step (the MX form of
+# csrc/paged_chunk_attn.hip) and the chunked prefill (the MX form of
+# csrc/paged_prefill_attn.hip)
 # ---------------------------------------------------------------------------
 
 def paged_attn_mx_available() -> bool:
@@ -2060,3 +2061,66 @@ def paged_chunk_attn_mx_step(q3: torch.Tensor, k3: torch.Tensor,
                          f"pages_per_seq={pps}, strides "
                          f"{[s.value for s in st]}")
     return ws[2]
+
+
+def paged_prefill_attn_mx_available() -> bool:
+    lib = _load()
+    return lib is not None and hasattr(lib, "paged_prefill_attn_mx")
+
+
+def paged_prefill_attn_mx_step(q3: torch.Tensor, k3: torch.Tensor,
+                               v3: torch.Tensor, k_pages: torch.Tensor,
+                               k_scale_pages: torch.Tensor,
+                               v_pages: torch.Tensor,
+                               v_scale_pages: torch.Tensor,
+                               block_table: torch.Tensor, cos: torch.Tensor,
+                               sin: torch.Tensor, pos_t: torch.Tensor,
+                               Hq: int, Hkv: int, scale: float,
+                               chunk_lens: Optional[torch.Tensor] = None
+                               ) -> torch.Tensor:
+    """:func:`paged_prefill_attn_step` over MXFP8 pages (``PagedMXKVCache``
+    pools, as for :func:`paged_attn_mx_step`; the MX form of
+    csrc/paged_prefill_attn.hip): any T >= 1 new tokens per sequence, meant
+    for T > 8, of which the first ``chunk_lens[b]`` are real (None: all T)
+    -> out (B, T, Hq*128).
+
+    With n = chunk_lens[b]: token t < n of sequence b is roped at
+    ``pos_t[b] + t``, K and V are quantized and stored in slot
+    ``(pos_t[b] + t) % 16`` of page ``block_table[b, (pos_t[b] + t) // 16]``
+    of all four pools (the bytes equal ``pack_mx(quantize_mx(row))``, those
+    of :func:`paged_chunk_attn_mx_step`), and the token attends rows
+    [0, pos_t[b] + t] as stored, the chunk's own rows in their quantized
+    form.  Tokens t >= n are padding: nothing is stored for them and their
+    output rows are zero.  The sequence is inactive (pools untouched, output
+    rows zero) unless ``1 <= n <= T``, ``0 <= pos_t[b]``,
+    ``pos_t[b] + n <= 16 * pages_per_seq`` and every entry
+    ``block_table[b, 0 .. (pos_t[b] + n - 1) // 16]`` lies in [0, num_pages);
+    no entry beyond that page is read, and rows at or beyond
+    ``pos_t[b] + n`` contribute nothing, whatever bytes they hold.  No device
+    sync and no atomics (hipGraph-capturable); a wrong dtype, shape, device
+    or stride raises ValueError and launches nothing."""
+    lib = _require_lib()
+    who = "paged_prefill_attn_mx_step"
+    if not paged_prefill_attn_mx_available():
+        raise RuntimeError("nxd_ops library has no paged_prefill_attn_mx — "
+                           "rebuild")
+    B = q3.shape[0] if q3.dim() == 3 else -1
+    num_pages, pps = _paged_mx_check_pools(
+        who, k_pages, k_scale_pages, v_pages, v_scale_pages, block_table, B,
+        Hkv)
+    dev = k_pages.device
+    T, st = _paged_prefill_check(who, q3, k3, v3, cos, sin, pos_t, chunk_lens,
+                                 B, Hq, Hkv, _PG_ROWS * pps, dev)
+    out = torch.empty(B, T, Hq * _DA_D, dtype=torch.bfloat16, device=dev)
+    lens = ctypes.c_void_p(None) if chunk_lens is None else _ptr(chunk_lens)
+    rc = lib.paged_prefill_attn_mx(
+        *map(_ptr, (q3, k3, v3, k_pages, k_scale_pages, v_pages,
+                    v_scale_pages, block_table, cos, sin, pos_t)), lens,
+        _ptr(out), B, T, Hq, Hkv, num_pages, pps, ctypes.c_float(scale), *st,
+        _stream())
+    if rc != 0:
+        raise ValueError(f"paged_prefill_attn_mx rejected B={B}, T={T}, "
+                         f"Hq={Hq}, Hkv={Hkv}, num_pages={num_pages}, "
+                         f"pages_per_seq={pps}, strides "
+                         f"{[s.value for s in st]}")
+    return out

@@ -13,6 +13,8 @@
 //   paged_chunk_attn.hip  the MX forms of paged_chunk_append (one thread per
 //                      32-block) and paged_chunk_part (the same dequant, in
 //                      chunk_attn_common.h)
+//   paged_prefill_attn.hip  the MX forms of paged_prefill_append (one thread
+//                      per 32-block) and paged_prefill_fwd (the same dequant)
 //   mx_skinny.hip      the fused quantizer: one lane per 16-element half
 //                      block, in the MFMA's operand layout
 //

@@ -76,9 +76,67 @@
 // workgroup per CU, as flash_fwd_kernel); paged_prefill_append 16 VGPRs,
 // 8448 B of LDS, occupancy 8.
 //
+// MXFP8 pages (paged_prefill_attn_mx, the MX = true forms of both kernels).
+// The pools are PagedMXKVCache's: e4m3 payload (num_pages, Hkv, 16, 128) and
+// biased e8m0 scales (num_pages, Hkv, 16, 4), all uint8.  Everything above
+// holds word for word; what differs is how a row reaches its page and how a
+// tile's rows reach the LDS image.
+//
+//   Append.  The new rows of the block's page are roped and copied into LDS
+//   as above; then thread t < 128 quantizes 32-block t & 3 of slot
+//   (t >> 2) & 15 of K (t < 64) or V with mxq_block32 and writes its 32
+//   payload bytes and its scale byte, new rows only: 16 rows x 4 blocks x 2
+//   operands.  The bytes are pack_mx(quantize_mx(row)), those that
+//   paged_chunk_append<true> and the one-token MX kernel store.
+//
+//   Staging map.  A tile is 64 x 128 payload bytes per operand, 512 threads x
+//   16 bytes: thread t owns row t >> 3, payload bytes 16 (t & 7) ..+15, and
+//   the row's four scale bytes as one aligned dword (the eight lanes of a row
+//   read the same dword, one request).  Wave w therefore stages rows 8w ..
+//   8w + 7, the same half of page 4j + (w >> 1) as in the bf16 map: pp_page,
+//   the one scalar id per wave and tile fetched a tile ahead, and "no lane
+//   selects a page" stay.  A lane keeps two offsets computed once, one into a
+//   payload page and one into a scale page, and carries 2 x 4 + 2 registers
+//   between load and LDS write where bf16 carries 16.
+//
+//   Write.  write_tile dequantizes with ca_deq8 / mxq_scale (e4m3 x e8m0 is
+//   exact in bf16) into bf16 chunks 2 (t & 7) and 2 (t & 7) + 1 of its row
+//   of the same dual-use image.  It sits where the bf16 write sits, after the
+//   tile's MFMA section, where the K and V fragments are dead; from the first
+//   img_row_read on the loop is one text for both formats.
+//
+//   Stale rows (at or beyond pos + n in the last tile) may hold 0xFF, the NaN
+//   encodings of e4m3 and e8m0: payload AND scale word are zeroed by SELECT
+//   before mxq_scale or the conversion sees them, never by a product
+//   (pc_load<true> of paged_chunk_attn.hip).  A wave whose page lies beyond
+//   `last` reads page 0 and zeroes it the same way.
+//
+//   The chunk's own rows are read back as stored: token t attends the MXFP8
+//   form of rows pos .. pos + t, as the torch chain does on the dequantized
+//   gather() after the paged write.
+//
+// Resources of the MX forms, measured as above: paged_prefill_fwd 238 VGPRs,
+// 0 AGPRs, 62-63 SGPRs, no scratch, no spills, the same LDS and occupancy 2;
+// paged_prefill_append 53 VGPRs, 46 SGPRs, 8448 B of LDS, occupancy 8.  The
+// bf16 forms keep the numbers above; the scale pools are the LAST kernel
+// arguments so that the kernarg offsets of everything else stay.
+//
+// Rejected for the MX forms:
+//   * a separate paged_prefill_attn_mx.hip: a third copy of the tile loop
+//     for a kernel that differs only in how a tile's rows reach the image
+//     (paged_chunk_attn.hip, for the same reason);
+//   * the block-scaled MFMA (v_mfma_scale_f32_32x32x64_f8f6f4): K's scales
+//     run along d and would fit the score product, but Q would have to be
+//     quantized to fp8, which changes the numerics of every format's
+//     prefill; V's scales run along d while the PV product contracts over
+//     rows, so they are no block scales of that contraction at all;
+//   * gathering the pages into a dense bf16 buffer and running
+//     paged_prefill_fwd<false>: the dense copy the pool exists to avoid, and
+//     a second pass over every row per layer and chunk.
+//
 // Layouts: q (B, T, Hq*128), k/v (B, T, Hkv*128) bf16 pre-RoPE with element
 // strides (batch, token) and a dense last dim; k_pages / v_pages bf16
-// (num_pages, Hkv, 16, 128) contiguous; block_table int32 (B, pages_per_seq)
+// (num_pages, Hkv, 16, 128) contiguous (MX: as above); block_table int32 (B, pages_per_seq)
 // contiguous; cos/sin (>= 16 * pages_per_seq, 64) fp32; pos_ptr B device
 // int64; len_ptr B device int64 or null (n[b] = T); out contiguous.
 
@@ -92,6 +150,7 @@
 #define PP_BUF_B (2 * TILE64_B)    // K image, then V image
 #define PP_LDS_B (2 * PP_BUF_B)    // two staging buffers: 65,536 B
 #define PP_APPEND_THREADS 256
+#define PP_SC (DA_D / 32)          // scale bytes of an MXFP8 row
 static_assert(PP_KV == 4 * PP_ROWS, "a tile is four pages");
 static_assert(PP_WAVES * 8 == PP_KV, "a wave stages half a page");
 
@@ -123,7 +182,11 @@ __device__ __forceinline__ bool pp_active(const long* __restrict__ pos_ptr,
 // 1. append: block (b, kvh, i), the i-th page the chunk touches
 // ---------------------------------------------------------------------------
 // Thread t: rows of parity t >> 7; of a row, threads u = t & 127 < 64 rope the
-// K pair (u, u + 64) and the others copy V elements (u - 64, u).
+// K pair (u, u + 64) and the others copy V elements (u - 64, u).  MX: the
+// pools are the uint8 payload pools, ksc / vsc the scale pools; thread
+// t < 128 then quantizes 32-block t & 3 of slot (t >> 2) & 15 of K (t < 64)
+// or V with mxq_block32 and stores its 32 payload bytes and its scale byte.
+template <bool MX>
 __global__ void __launch_bounds__(PP_APPEND_THREADS)
 paged_prefill_append(const short* __restrict__ kin,
                      const short* __restrict__ vin, short* __restrict__ kpages,
@@ -133,7 +196,8 @@ paged_prefill_append(const short* __restrict__ kin,
                      const float* __restrict__ sinp,
                      const long* __restrict__ pos_ptr,
                      const long* __restrict__ len_ptr, int T, int Hkv,
-                     int num_pages, int pages_per_seq, long kv_bs, long kv_ts) {
+                     int num_pages, int pages_per_seq, long kv_bs, long kv_ts,
+                     uint8_t* __restrict__ ksc, uint8_t* __restrict__ vsc) {
   const int kvh = blockIdx.x;
   const int b = blockIdx.z;
   const int tid = threadIdx.x;
@@ -165,15 +229,35 @@ paged_prefill_append(const short* __restrict__ kin,
     }
   }
   __syncthreads();
-  // 2 x 16 rows x 16 chunks of 16 bytes: two per thread, new rows only
-  const long dst = ((long)pg * Hkv + kvh) * PP_ROWS * DA_D;
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int slot = tid >> 4, c16 = tid & 15;
+  if constexpr (MX) {
+    // 2 x 16 rows x 4 blocks of 32 elements: one per thread of the first
+    // 128, new rows only; nothing else of the slot's page is touched
+    const int opv = tid >> 6, slot = (tid >> 2) & 15, blk = tid & 3;
     const int row = PP_ROWS * page + slot;
-    if (row >= r0 && row < r1)
-      *(uint4v*)((i ? vpages : kpages) + dst + slot * DA_D + 8 * c16) =
-          *(const uint4v*)&rows[i][slot][8 * c16];
+    if (tid < 128 && row >= r0 && row < r1) {
+      const s8v* in = (const s8v*)&rows[opv][slot][32 * blk];
+      s8v x[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) x[i] = in[i];
+      uint4v out[2];
+      const int e = mxq_block32(x, out);
+      const long dst = ((long)pg * Hkv + kvh) * PP_ROWS + slot;  // the row
+      uint8_t* pay = (uint8_t*)(opv ? vpages : kpages) + dst * DA_D + 32 * blk;
+      ((uint4v*)pay)[0] = out[0];
+      ((uint4v*)pay)[1] = out[1];
+      (opv ? vsc : ksc)[dst * PP_SC + blk] = (uint8_t)(e + 127);
+    }
+  } else {
+    // 2 x 16 rows x 16 chunks of 16 bytes: two per thread, new rows only
+    const long dst = ((long)pg * Hkv + kvh) * PP_ROWS * DA_D;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int slot = tid >> 4, c16 = tid & 15;
+      const int row = PP_ROWS * page + slot;
+      if (row >= r0 && row < r1)
+        *(uint4v*)((i ? vpages : kpages) + dst + slot * DA_D + 8 * c16) =
+            *(const uint4v*)&rows[i][slot][8 * c16];
+    }
   }
 }
 
@@ -209,7 +293,7 @@ __device__ __forceinline__ void pp_store_zero(short* __restrict__ op, int b,
 // workgroup per CU, as for flash_fwd_kernel; the 64 KB of LDS would admit a
 // second, the 245 VGPRs of the O^T accumulators and the Q, K and V fragments
 // do not.
-template <int REP>
+template <int REP, bool MX>
 __global__ void __launch_bounds__(PP_THREADS, 2)
 paged_prefill_fwd(const short* __restrict__ qin,
                   const short* __restrict__ kpages,
@@ -220,7 +304,9 @@ paged_prefill_fwd(const short* __restrict__ qin,
                   const long* __restrict__ pos_ptr,
                   const long* __restrict__ len_ptr, short* __restrict__ op,
                   int T, int Hkv, int num_pages, int pages_per_seq,
-                  float scale, long q_bs, long q_ts) {
+                  float scale, long q_bs, long q_ts,
+                  const uint8_t* __restrict__ ksc,
+                  const uint8_t* __restrict__ vsc) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int TOK = PP_QW * PP_WAVES / REP;  // tokens of a workgroup
 
@@ -292,31 +378,66 @@ paged_prefill_fwd(const short* __restrict__ qin,
 
   // ---- staging: thread t owns rows {2 (t >> 4), 2 (t >> 4) + 1} of the
   // tile at 16-byte chunk t & 15; the wave's eight rows are slots
-  // 8 (wid & 1) .. + 7 of ONE page
-  const int st_c16 = tid & 15;
-  const int st_r0 = 2 * (tid >> 4), st_r1 = st_r0 + 1;
+  // 8 (wid & 1) .. + 7 of ONE page.  MX (file header): row t >> 3, payload
+  // bytes 16 (t & 7) ..+15 and the row's scale dword; kreg[1] / vreg[1] are
+  // unused, lane_off is the byte offset into a payload page and sc_off the
+  // one into a scale page.
+  const int st_c16 = MX ? tid & 7 : tid & 15;
+  const int st_r0 = MX ? tid >> 3 : 2 * (tid >> 4), st_r1 = st_r0 + 1;
   const long page_elems = (long)Hkv * PP_ROWS * DA_D;
+  const long page_sc = (long)Hkv * PP_ROWS * PP_SC;
   const long lane_off =
-      ((long)kvh * PP_ROWS + 8 * (wid & 1) + 2 * (lane >> 4)) * DA_D +
-      8 * st_c16;
+      MX ? ((long)kvh * PP_ROWS + 8 * (wid & 1) + (lane >> 3)) * DA_D +
+               16 * st_c16
+         : ((long)kvh * PP_ROWS + 8 * (wid & 1) + 2 * (lane >> 4)) * DA_D +
+               8 * st_c16;
+  const long sc_off =
+      ((long)kvh * PP_ROWS + 8 * (wid & 1) + (lane >> 3)) * PP_SC;
 
   uint4v kreg[2], vreg[2];
+  unsigned ksw = 0, vsw = 0;  // MX: the scale dwords of the thread's row
   auto issue_loads = [&](int t, int pg) {
     const long off = (long)pg * page_elems + lane_off;
     const bool ok0 = PP_KV * t + st_r0 < n_rows;
-    const bool ok1 = PP_KV * t + st_r1 < n_rows;
-    kreg[0] = ca_sel(ok0, *(const uint4v*)(kpages + off));
-    kreg[1] = ca_sel(ok1, *(const uint4v*)(kpages + off + DA_D));
-    vreg[0] = ca_sel(ok0, *(const uint4v*)(vpages + off));
-    vreg[1] = ca_sel(ok1, *(const uint4v*)(vpages + off + DA_D));
+    if constexpr (MX) {
+      // stale rows (and page 0 standing in for a page beyond `last`) may
+      // hold NaN bytes: payload and scale word are zeroed by select
+      const long soff = (long)pg * page_sc + sc_off;
+      kreg[0] = ca_sel(ok0, *(const uint4v*)((const uint8_t*)kpages + off));
+      vreg[0] = ca_sel(ok0, *(const uint4v*)((const uint8_t*)vpages + off));
+      const unsigned ks = *(const unsigned*)(ksc + soff);
+      const unsigned vs = *(const unsigned*)(vsc + soff);
+      ksw = ok0 ? ks : 0u;
+      vsw = ok0 ? vs : 0u;
+    } else {
+      const bool ok1 = PP_KV * t + st_r1 < n_rows;
+      kreg[0] = ca_sel(ok0, *(const uint4v*)(kpages + off));
+      kreg[1] = ca_sel(ok1, *(const uint4v*)(kpages + off + DA_D));
+      vreg[0] = ca_sel(ok0, *(const uint4v*)(vpages + off));
+      vreg[1] = ca_sel(ok1, *(const uint4v*)(vpages + off + DA_D));
+    }
   };
   auto write_tile = [&](int buf) {
     char* kimg = smem + buf * PP_BUF_B;
     char* vimg = kimg + TILE64_B;
-    *(uint4v*)(kimg + img_off(st_r0, st_c16)) = kreg[0];
-    *(uint4v*)(kimg + img_off(st_r1, st_c16)) = kreg[1];
-    *(uint4v*)(vimg + img_off(st_r0, st_c16)) = vreg[0];
-    *(uint4v*)(vimg + img_off(st_r1, st_c16)) = vreg[1];
+    if constexpr (MX) {
+      // dequantized here, after the tile's MFMA section: bf16 chunks
+      // 2 (t & 7) and 2 (t & 7) + 1 of the row, both of 32-block (t & 7) >> 1
+      const int sh = 8 * (st_c16 >> 1);
+      const float kscale = mxq_scale((ksw >> sh) & 0xff);
+      const float vscale = mxq_scale((vsw >> sh) & 0xff);
+      const int o0 = img_off(st_r0, 2 * st_c16);
+      const int o1 = img_off(st_r0, 2 * st_c16 + 1);
+      *(uint4v*)(kimg + o0) = ca_deq8(kreg[0][0], kreg[0][1], kscale);
+      *(uint4v*)(kimg + o1) = ca_deq8(kreg[0][2], kreg[0][3], kscale);
+      *(uint4v*)(vimg + o0) = ca_deq8(vreg[0][0], vreg[0][1], vscale);
+      *(uint4v*)(vimg + o1) = ca_deq8(vreg[0][2], vreg[0][3], vscale);
+    } else {
+      *(uint4v*)(kimg + img_off(st_r0, st_c16)) = kreg[0];
+      *(uint4v*)(kimg + img_off(st_r1, st_c16)) = kreg[1];
+      *(uint4v*)(vimg + img_off(st_r0, st_c16)) = vreg[0];
+      *(uint4v*)(vimg + img_off(st_r1, st_c16)) = vreg[1];
+    }
   };
 
   const int row_base = img_row_base(col, hi);
@@ -469,16 +590,18 @@ paged_prefill_fwd(const short* __restrict__ qin,
 // len_ptr may be null (every token is real).  Returns non-zero, launching
 // nothing, outside the contract: T < 1, rep not in {1, 2, 4, 8}, sizes or
 // strides that do not hold a row or break the aligned loads, num_pages < 1 or
-// pages_per_seq < 1.
-extern "C" int paged_prefill_attn(const void* q, const void* k, const void* v,
-                                  void* kpages, void* vpages,
-                                  const void* block_table, const void* cosp,
-                                  const void* sinp, const void* pos_ptr,
-                                  const void* len_ptr, void* outp, int B, int T,
-                                  int Hq, int Hkv, int num_pages,
-                                  int pages_per_seq, float scale, long q_bs,
-                                  long q_ts, long kv_bs, long kv_ts,
-                                  hipStream_t stream) {
+// pages_per_seq < 1, or pools that break the aligned loads: 16 bytes for the
+// bf16 and the payload pools, 4 for the scale pools (a row's scales are one
+// dword).
+template <bool MX>
+static int pp_launch(const void* q, const void* k, const void* v, void* kpages,
+                     void* ksc, void* vpages, void* vsc,
+                     const void* block_table, const void* cosp,
+                     const void* sinp, const void* pos_ptr,
+                     const void* len_ptr, void* outp, int B, int T, int Hq,
+                     int Hkv, int num_pages, int pages_per_seq, float scale,
+                     long q_bs, long q_ts, long kv_bs, long kv_ts,
+                     hipStream_t stream) {
   if (num_pages < 1 || pages_per_seq < 1 ||
       pages_per_seq > 0x7FFFFFFF / PP_ROWS - 1 || T < 1 ||
       T > 0x7FFFFFFF - PP_ROWS * (pages_per_seq + 1))
@@ -494,25 +617,60 @@ extern "C" int paged_prefill_attn(const void* q, const void* k, const void* v,
       ((uintptr_t)k | (uintptr_t)v) % 2 || (uintptr_t)block_table % 4 ||
       (uintptr_t)pos_ptr % 8 || (uintptr_t)len_ptr % 8)
     return 1;
+  if (MX && ((uintptr_t)ksc | (uintptr_t)vsc) % 4) return 1;
   const int rep = Hq / Hkv;
   const int tok = PP_QW * PP_WAVES / rep;
   const long nblk = ((long)T + tok - 1) / tok;
   const long npg = ((long)T + 2 * PP_ROWS - 2) / PP_ROWS;  // pages of a chunk
   if (nblk > 65535 || npg > 65535) return 1;
-  paged_prefill_append<<<dim3(Hkv, (unsigned)npg, B), PP_APPEND_THREADS, 0,
-                         stream>>>(
+  paged_prefill_append<MX><<<dim3(Hkv, (unsigned)npg, B), PP_APPEND_THREADS,
+                             0, stream>>>(
       (const short*)k, (const short*)v, (short*)kpages, (short*)vpages,
       (const int*)block_table, (const float*)cosp, (const float*)sinp,
       (const long*)pos_ptr, (const long*)len_ptr, T, Hkv, num_pages,
-      pages_per_seq, kv_bs, kv_ts);
+      pages_per_seq, kv_bs, kv_ts, (uint8_t*)ksc, (uint8_t*)vsc);
   da_for_rep(rep, [&](auto r) {
     constexpr int R = decltype(r)::value;
-    paged_prefill_fwd<R><<<dim3(Hkv, (unsigned)nblk, B), PP_THREADS, PP_LDS_B,
-                           stream>>>(
+    paged_prefill_fwd<R, MX><<<dim3(Hkv, (unsigned)nblk, B), PP_THREADS,
+                               PP_LDS_B, stream>>>(
         (const short*)q, (const short*)kpages, (const short*)vpages,
         (const int*)block_table, (const float*)cosp, (const float*)sinp,
         (const long*)pos_ptr, (const long*)len_ptr, (short*)outp, T, Hkv,
-        num_pages, pages_per_seq, scale, q_bs, q_ts);
+        num_pages, pages_per_seq, scale, q_bs, q_ts, (const uint8_t*)ksc,
+        (const uint8_t*)vsc);
   });
   return 0;
+}
+
+extern "C" int paged_prefill_attn(const void* q, const void* k, const void* v,
+                                  void* kpages, void* vpages,
+                                  const void* block_table, const void* cosp,
+                                  const void* sinp, const void* pos_ptr,
+                                  const void* len_ptr, void* outp, int B, int T,
+                                  int Hq, int Hkv, int num_pages,
+                                  int pages_per_seq, float scale, long q_bs,
+                                  long q_ts, long kv_bs, long kv_ts,
+                                  hipStream_t stream) {
+  return pp_launch<false>(q, k, v, kpages, nullptr, vpages, nullptr,
+                          block_table, cosp, sinp, pos_ptr, len_ptr, outp, B,
+                          T, Hq, Hkv, num_pages, pages_per_seq, scale, q_bs,
+                          q_ts, kv_bs, kv_ts, stream);
+}
+
+// The same over MXFP8 pages: kpay / vpay uint8 (num_pages, Hkv, 16, 128), ksc
+// / vsc uint8 (num_pages, Hkv, 16, 4).
+extern "C" int paged_prefill_attn_mx(const void* q, const void* k,
+                                     const void* v, void* kpay, void* ksc,
+                                     void* vpay, void* vsc,
+                                     const void* block_table, const void* cosp,
+                                     const void* sinp, const void* pos_ptr,
+                                     const void* len_ptr, void* outp, int B,
+                                     int T, int Hq, int Hkv, int num_pages,
+                                     int pages_per_seq, float scale, long q_bs,
+                                     long q_ts, long kv_bs, long kv_ts,
+                                     hipStream_t stream) {
+  return pp_launch<true>(q, k, v, kpay, ksc, vpay, vsc, block_table, cosp,
+                         sinp, pos_ptr, len_ptr, outp, B, T, Hq, Hkv,
+                         num_pages, pages_per_seq, scale, q_bs, q_ts, kv_bs,
+                         kv_ts, stream);
 }
