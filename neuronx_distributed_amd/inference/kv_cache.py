@@ -46,6 +46,46 @@ class KVCache:
         self.v[:, :, pos:pos + S] = v_new
         return self.k[:, :, :pos + S], self.v[:, :, :pos + S]
 
+    def commit_path(self, pos: torch.Tensor, path: torch.Tensor) -> None:
+        """After a tree step at the device position ``pos`` (one element, or
+        one per sequence): pack the accepted root path down to consecutive
+        rows.  ``path`` (B, L) integer, L <= 16: column 0 is the root, then
+        the accepted node indices, then -1.  Row ``pos + d`` takes what row
+        ``pos + path[b, d]`` held for every d >= 1 with a valid entry; all
+        sources are read before any row is written.  Entries that are
+        negative, 16 or more, or whose rows fall outside the cache move
+        nothing.  No host sync.  ops.tree_kv_commit on a bf16 GPU cache with
+        head dim 128, torch index ops otherwise."""
+        from .. import ops
+
+        if type(self) is not KVCache:
+            raise NotImplementedError(
+                f"commit_path needs a plain KVCache, not "
+                f"{type(self).__name__}")
+        B, _, Smax, D = self.k.shape
+        ragged = _is_ragged(pos, B)
+        if self.k.is_cuda and self.k.dtype == torch.bfloat16 and D == 128 \
+                and ops.tree_attn_available():
+            ops.tree_kv_commit(
+                self.k, self.v,
+                pos.reshape(B).contiguous() if ragged else pos.reshape(1),
+                path.to(torch.int32).contiguous(), ragged=ragged)
+            return
+        L = path.shape[1]
+        node = path.long()
+        pos_b = pos.reshape(-1, 1).expand(B, 1)
+        d = torch.arange(L, device=path.device).view(1, L)
+        ok = (d >= 1) & (node >= 0) & (node < 16) & (pos_b >= 0) \
+            & (pos_b + torch.maximum(node, d) < Smax)
+        # an entry that moves nothing rewrites row pos (clamped) with itself;
+        # no valid entry writes there, its d being at least 1
+        keep = pos_b.clamp(0, Smax - 1).expand(B, L)
+        src = torch.where(ok, pos_b + node, keep).view(B, 1, L, 1)
+        dst = torch.where(ok, pos_b + d, keep).view(B, 1, L, 1)
+        for buf in (self.k, self.v):
+            shape = (B, buf.shape[1], L, D)
+            buf.scatter_(2, dst.expand(shape), buf.gather(2, src.expand(shape)))
+
 
 def _chunk_rows(pos: torch.Tensor, S: int) -> torch.Tensor:
     """Cache row indices of S new tokens at the device position ``pos``:

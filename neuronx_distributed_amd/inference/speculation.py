@@ -251,23 +251,117 @@ def speculative_generate(target, draft, input_ids: torch.Tensor,
     return tokens, rate
 
 
+def _medusa_tree(target, heads, input_ids, max_new_tokens, medusa_choices,
+                 caches):
+    """medusa_generate(medusa_choices=...): every round verifies the whole
+    candidate tree in ONE forward at per-sequence device positions, each
+    sequence accepts its own longest root path, and the accepted rows are
+    packed down in every layer's cache (KVCache.commit_path)."""
+    from ..utils.medusa_utils import (generate_medusa_buffers,
+                                      medusa_tree_topology)
+
+    B, S = input_ids.shape
+    dev = input_ids.device
+    buf = generate_medusa_buffers(medusa_choices, device=dev)
+    tree = medusa_tree_topology(buf["medusa_attn_mask"], device=dev)
+    tree_indices, retrieve = buf["tree_indices"], buf["retrieve_indices"]
+    P, L = retrieve.shape                      # root paths, depth + 1
+    max_k = max(p[-1] for p in medusa_choices) + 1
+    if L - 1 > len(heads):
+        raise ValueError(f"a choice tree of depth {L - 1} needs as many "
+                         f"heads, got {len(heads)}")
+    if max_new_tokens < 1:
+        raise ValueError(f"max_new_tokens {max_new_tokens} must be at least 1")
+    node = retrieve.clamp(min=0)               # (P, L)
+    parent = torch.cat([node[:, :1], node[:, :-1]], dim=1)
+    steps = torch.arange(L, device=dev)
+
+    hidden = target.model(input_ids, pos_offset=0, kv_caches=caches)
+    tok = _greedy(target.lm_head(hidden[:, -1:, :])[:, 0])
+    h_last = hidden[:, -1, :]
+    new = input_ids.new_zeros((B, max_new_tokens + L))
+    new[:, 0] = tok
+    produced = torch.ones(B, dtype=torch.long, device=dev)
+    pos = torch.where(produced < max_new_tokens, torch.full_like(produced, S),
+                      -torch.ones_like(produced))
+    n_accepted = torch.zeros((), dtype=torch.long, device=dev)
+    n_row_rounds = 0
+
+    while True:
+        act = pos >= 0
+        n_act = int(act.sum())
+        if n_act == 0:
+            break
+        n_row_rounds += n_act
+        # 1. the T candidates: the last token, then each head's top-k
+        topk = [heads[i](h_last).topk(max_k, dim=-1).indices
+                for i in range(L - 1)]
+        cand = torch.cat([tok.unsqueeze(1)] + topk, dim=1)[:, tree_indices]
+        # 2., 3. one tree forward; the target's greedy token at every node
+        hidden = target.model(cand, pos_offset=pos, kv_caches=caches,
+                              tree=tree)
+        tgt = _greedy(target.lm_head(hidden))  # (B, T)
+        # 4. per sequence the longest root path on which every node's token
+        # is the target's token at its parent
+        ok = (cand[:, node] == tgt[:, parent]) & (retrieve >= 0)  # (B, P, L)
+        ok[:, :, 0] = True
+        n_ok = ok.long().cumprod(dim=2).sum(dim=2) - 1            # (B, P)
+        j, best = n_ok.max(dim=1)                                 # (B,)
+        path = torch.where(steps.view(1, L) <= j.view(B, 1), node[best],
+                           -torch.ones_like(node[best]))          # (B, L)
+        # 5. the accepted rows move to pos + 1 .. pos + j
+        for c in caches:
+            c.commit_path(pos, path)
+        # 6., 7. the path's target tokens are the output; the last one and
+        # its hidden state start the next round
+        emit = tgt.gather(1, path.clamp(min=0))                   # (B, L)
+        idx = torch.where(act.view(B, 1), produced.view(B, 1) + steps,
+                          steps.expand(B, -1))
+        new.scatter_(1, idx, torch.where(act.view(B, 1), emit,
+                                         new.gather(1, idx)))
+        last = node[best].gather(1, j.view(B, 1))                 # (B, 1)
+        tok = tgt.gather(1, last).view(B)
+        h_last = hidden.gather(
+            1, last.view(B, 1, 1).expand(B, 1, hidden.shape[-1]))[:, 0]
+        n_accepted += (j * act).sum()
+        produced = produced + (j + 1) * act
+        pos = torch.where(act & (produced < max_new_tokens), pos + j + 1,
+                          -torch.ones_like(pos))
+
+    tokens = torch.cat([input_ids, new[:, :max_new_tokens]], dim=1)
+    return tokens, int(n_accepted) / max(1, n_row_rounds * (L - 1))
+
+
 @torch.no_grad()
 def medusa_generate(target, medusa_heads, input_ids: torch.Tensor,
                     max_new_tokens: int = 32, kv_format=None,
-                    fused_verify: bool = False):
+                    fused_verify: bool = False, medusa_choices=None):
     """Medusa-style speculation: ``medusa_heads`` (iterable of
     utils.medusa_utils.MedusaHead, head i predicting the token at offset
     i+2) propose a chain from the LAST HIDDEN STATE in one shot — no
     autoregressive draft model — and the target verifies the chunk exactly
     like :func:`speculative_generate`.  Greedy output is identical to
     plain generation.  ``fused_verify``: as in :func:`speculative_generate`,
-    for the verify chunk."""
+    for the verify chunk.
+
+    ``medusa_choices``: a choice tree as taken by
+    utils.medusa_utils.generate_medusa_buffers, at most 15 entries.  Head i
+    then proposes its top-k tokens and the whole tree of candidates is
+    verified in one forward per round (LlamaAttention._tree_step), each
+    sequence accepting its own longest path.  Tree mode works on the plain
+    cache only and always at device positions, so ``fused_verify`` has no
+    say in it: the fused kernel runs wherever the tree step can take it."""
     from ..utils.sampling import Sampler
 
     sampler = Sampler(do_sample=False)
     heads = list(medusa_heads)
     k = len(heads)
     B, S = input_ids.shape
+    if medusa_choices is not None:
+        if kv_format is not None:
+            raise ValueError(f"medusa_choices needs the plain cache, not "
+                             f"kv_format={kv_format!r}")
+        k = len(medusa_choices)   # T - 1 spare rows for the last round
 
     from ..parallel import parallel_state as ps
 
@@ -277,7 +371,12 @@ def medusa_generate(target, medusa_heads, input_ids: torch.Tensor,
     n_kv_local = cfg.num_key_value_heads * kv_mult // tp
     caches = build_kv_caches(cfg.num_hidden_layers, B, n_kv_local,
                              S + max_new_tokens + k + 1, cfg.head_dim,
-                             device=input_ids.device, kv_format=kv_format)
+                             device=input_ids.device, kv_format=kv_format,
+                             **({} if medusa_choices is None else
+                                {"dtype": next(target.parameters()).dtype}))
+    if medusa_choices is not None:
+        return _medusa_tree(target, heads, input_ids, max_new_tokens,
+                            medusa_choices, caches)
 
     hidden = target.model(input_ids, pos_offset=0, kv_caches=caches)
     tok = sampler(target.lm_head(hidden)[:, -1, :])

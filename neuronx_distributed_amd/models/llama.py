@@ -195,11 +195,16 @@ class LlamaAttention(nn.Module):
             init_method=_init_method(config.initializer_range))
 
     def forward(self, hidden, cos, sin, pos_offset=0, kv_cache=None,
-                chunk_lens=None):
+                chunk_lens=None, tree=None):
         """``chunk_lens`` (B,) int64 on the device: chunked prefill on a
         PagedKVCache.  Only the first chunk_lens[b] of the S > 8 tokens at the
         device-tensor position are real, the others are padding
-        (:meth:`_cached_step`)."""
+        (:meth:`_cached_step`).
+
+        ``tree``: the ``(anc, depth)`` int32 pair of
+        ``utils.medusa_utils.medusa_tree_topology``.  The S = 2..16 tokens at
+        the device-tensor position are the nodes of a candidate tree, not a
+        chain (:meth:`_tree_step`)."""
         sp = self.config.sequence_parallel_enabled
         q, k, v = self.qkv_proj(hidden)
         if sp:
@@ -215,6 +220,11 @@ class LlamaAttention(nn.Module):
             # full-cache masked attention (no dynamic shapes)
             from ..inference.kv_cache import PagedKVCache, PagedMXKVCache
 
+            if tree is not None:
+                if chunk_lens is not None:
+                    raise ValueError("tree and chunk_lens do not combine")
+                return self._cached_step(q, k, v, cos, sin, pos_offset,
+                                         kv_cache, sp, tree=tree)
             # a longer chunk: chunked prefill, on a paged cache only
             if not 1 <= S <= 8 and (S < 1 or type(kv_cache) not in (
                     PagedKVCache, PagedMXKVCache)):
@@ -228,8 +238,9 @@ class LlamaAttention(nn.Module):
                     f"got {S}: the steps of 1..8 tokens have no padding")
             return self._cached_step(q, k, v, cos, sin, pos_offset, kv_cache,
                                      sp, chunk_lens)
-        if chunk_lens is not None:
-            raise ValueError("chunk_lens needs a device-tensor position")
+        if chunk_lens is not None or tree is not None:
+            raise ValueError("chunk_lens and tree need a device-tensor "
+                             "position")
         q, k = ops.apply_rotary_pos_emb(q, k, cos, sin, pos_offset)
 
         # (B,S,h,D) -> (B,h,S,D)
@@ -255,7 +266,7 @@ class LlamaAttention(nn.Module):
         return self.o_proj(out)
 
     def _cached_step(self, q, k, v, cos, sin, pos_t, kv_cache, sp,
-                     chunk_lens=None):
+                     chunk_lens=None, tree=None):
         """S = 1..8 new tokens at the device position ``pos_t`` (shape (1,)):
         token t is roped at pos + t, written to cache row pos + t and attends
         rows [0, pos + t].  Everything derives from the device tensor, so the
@@ -301,10 +312,15 @@ class LlamaAttention(nn.Module):
         ops.paged_chunk_attn_mx_available() as well, and S > 8 (with
         ``chunk_lens`` as above) through ops.paged_prefill_attn_mx_step where
         ops.paged_prefill_attn_mx_available() as well; everything else takes
-        the torch chain on the dequantized kv_cache.gather()."""
+        the torch chain on the dequantized kv_cache.gather().
+
+        With ``tree`` the S tokens are tree nodes: :meth:`_tree_step`."""
         from ..inference.kv_cache import (KVCache, MXKVCache, PagedKVCache,
                                           PagedMXKVCache)
 
+        if tree is not None:
+            return self._tree_step(q, k, v, cos, sin, pos_t, kv_cache, sp,
+                                   tree)
         B, S = q.shape[0], q.shape[1]
         paged_mx = type(kv_cache) is PagedMXKVCache
         paged = paged_mx or type(kv_cache) is PagedKVCache
@@ -511,6 +527,108 @@ class LlamaAttention(nn.Module):
             out = out.transpose(0, 1)
         return self.o_proj(out)
 
+    def _tree_step(self, q, k, v, cos, sin, pos_t, kv_cache, sp, tree):
+        """S = 2..16 nodes of a candidate tree at the device position
+        ``pos_t`` (one element, or one per sequence).  ``tree = (anc, depth)``
+        int32 (S,): node i is roped at pos + depth[i], written to cache row
+        pos + i, and attends rows [0, pos) plus the new rows pos + j whose bit
+        j is set in anc[i] (itself and its ancestors).  A sequence whose S
+        rows do not all lie in the cache is inactive, with either kind of
+        position: its cache rows stay and its output is zero.
+
+        On GPU with D = 128, bf16 and a plain bf16 KVCache the whole chain is
+        ops.tree_attn_step where ops.tree_attn_available() and rep * S <= 64;
+        everything else takes the torch chain below (the reference)."""
+        from ..inference.kv_cache import KVCache
+
+        anc, depth = tree
+        B, S = q.shape[0], q.shape[1]
+        if type(kv_cache) is not KVCache:
+            raise ValueError(
+                f"a tree step needs a plain KVCache, got "
+                f"{type(kv_cache).__name__}")
+        if not 2 <= S <= 16 or anc.numel() != S or depth.numel() != S:
+            raise ValueError(
+                f"a tree step takes 2..16 nodes with anc and depth of that "
+                f"length, got {S} tokens, anc {tuple(anc.shape)}, depth "
+                f"{tuple(depth.shape)}")
+        if pos_t.numel() not in (1, B):
+            raise ValueError(
+                f"a device-tensor position holds one element, or one per "
+                f"sequence ({B}), got {tuple(pos_t.shape)}")
+        ragged = B > 1 and pos_t.numel() == B
+        rep = self.num_heads_local // self.num_kv_local
+        scale = 1.0 / math.sqrt(self.head_dim)
+        fusable = (q.is_cuda and self.head_dim == 128 and rep in (1, 2, 4, 8)
+                   and q.dtype == torch.bfloat16
+                   and self.sliding_window is None
+                   and kv_cache.k.dtype == torch.bfloat16
+                   and kv_cache.k.is_cuda and rep * S <= 64
+                   and ops.tree_attn_available()
+                   and (not ragged or ops.ragged_attn_enabled()))
+        if fusable:
+            def _flat(t):
+                f = t.reshape(B, S, -1)
+                ok = (f.stride(2) == 1 and f.stride(1) >= f.shape[2]
+                      and f.stride(0) % 8 == 0 and f.stride(1) % 8 == 0
+                      and f.data_ptr() % 16 == 0)
+                return f if ok else f.contiguous()
+
+            qf, kf, vf = _flat(q), _flat(k), _flat(v)
+            if kf.stride() != vf.stride():
+                kf, vf = kf.contiguous(), vf.contiguous()
+            out = ops.tree_attn_step(
+                qf, kf, vf, kv_cache.k, kv_cache.v, cos, sin,
+                pos_t.reshape(B).contiguous() if ragged else pos_t.reshape(1),
+                anc, depth, self.num_heads_local, self.num_kv_local, scale,
+                ragged=ragged)
+            if sp:
+                out = out.transpose(0, 1)
+            return self.o_proj(out)
+        half = self.head_dim // 2
+        Smax = kv_cache.k.shape[2]
+        dev = q.device
+        pos_b = pos_t.reshape(-1, 1).expand(B, 1)
+        active = (pos_b >= 0) & (pos_b + S <= Smax)              # (B, 1)
+        base = torch.where(active, pos_b, 0)
+        rows = (base + depth.to(dev).long().clamp(0, S - 1)).reshape(-1)
+        c = cos.index_select(0, rows).view(B, S, 1, half)
+        s = sin.index_select(0, rows).view(B, S, 1, half)
+
+        def rope(x):
+            x0 = x[..., :half].float()
+            x1 = x[..., half:].float()
+            return torch.cat([x0 * c - x1 * s, x1 * c + x0 * s],
+                             dim=-1).to(x.dtype)
+
+        q = rope(q).transpose(1, 2)  # (B,h,S,D)
+        k = rope(k).transpose(1, 2)
+        v = v.transpose(1, 2)
+        # always the per-sequence write: it leaves an inactive sequence alone
+        K, V = kv_cache.k, kv_cache.v
+        from ..inference.kv_cache import _ragged_write
+        _ragged_write(pos_b, (K, k.to(K.dtype)), (V, v.to(V.dtype)))
+        if K.dtype != q.dtype:
+            K, V = K.to(q.dtype), V.to(q.dtype)
+        qg = q.reshape(B, self.num_kv_local, rep * S, self.head_dim)
+        scores = (qg @ K.transpose(-1, -2)).float() * scale
+        scores = scores.view(B, self.num_kv_local, rep, S, Smax)
+        # (B, S, Smax): old rows, or a new row whose bit is set
+        j = torch.arange(Smax, device=dev).view(1, 1, Smax) - base.view(B, 1, 1)
+        bits = (anc.to(dev).long().view(1, S, 1) >> j.clamp(0, S - 1)) & 1
+        seen = (j < 0) | ((j < S) & (bits == 1))
+        seen = seen | ((j == 0) & ~active.view(B, 1, 1))  # zeroed below
+        scores = scores.masked_fill(~seen.view(B, 1, 1, S, Smax),
+                                    float("-inf"))
+        probs = torch.softmax(scores, dim=-1).to(q.dtype)
+        out = probs.view(B, self.num_kv_local, rep * S, Smax) @ V
+        out = out.view(B, self.num_heads_local, S, self.head_dim)
+        out = out.transpose(1, 2).reshape(B, S, -1)
+        out = torch.where(active.view(B, 1, 1), out, 0)
+        if sp:
+            out = out.transpose(0, 1)
+        return self.o_proj(out)
+
 
 class LlamaMLP(nn.Module):
     def __init__(self, config: LlamaConfig):
@@ -573,14 +691,14 @@ class LlamaDecoderLayer(nn.Module):
             sequence_parallel_enabled=sp)
 
     def forward(self, hidden, cos, sin, pos_offset=0, kv_cache=None,
-                chunk_lens=None):
+                chunk_lens=None, tree=None):
         h = hidden + self.self_attn(self.input_layernorm(hidden), cos, sin,
                                     pos_offset, kv_cache,
-                                    chunk_lens=chunk_lens)
+                                    chunk_lens=chunk_lens, tree=tree)
         return h + self.mlp(self.post_attention_layernorm(h))
 
     def forward_fused(self, residual, delta, cos, sin, pos_offset, kv_cache,
-                      chunk_lens=None):
+                      chunk_lens=None, tree=None):
         """Inference path carrying (residual, delta) so every residual-add
         fuses into the next RMSNorm (ops.add_rmsnorm): 2 elementwise kernels
         per layer instead of 4.  hidden == residual + delta."""
@@ -591,7 +709,7 @@ class LlamaDecoderLayer(nn.Module):
                 residual, delta, self.input_layernorm.weight,
                 self.input_layernorm.variance_epsilon)
         attn_out = self.self_attn(normed, cos, sin, pos_offset, kv_cache,
-                                  chunk_lens=chunk_lens)
+                                  chunk_lens=chunk_lens, tree=tree)
         residual, normed2 = ops.add_rmsnorm(
             residual, attn_out, self.post_attention_layernorm.weight,
             self.post_attention_layernorm.variance_epsilon)
@@ -646,10 +764,12 @@ class LlamaModel(nn.Module):
             self.rope_sin.copy_(sin)
 
     def forward(self, input_ids, pos_offset=0, kv_caches=None,
-                chunk_lens=None):
-        # chunk_lens: LlamaAttention.forward; passed on only when given, so
-        # layers of other families keep their signatures
+                chunk_lens=None, tree=None):
+        # chunk_lens, tree: LlamaAttention.forward; passed on only when
+        # given, so layers of other families keep their signatures
         kw = {} if chunk_lens is None else {"chunk_lens": chunk_lens}
+        if tree is not None:
+            kw["tree"] = tree
         hidden = self.embed_tokens(input_ids)  # (B,S,H)
         if self.config.sequence_parallel_enabled:
             hidden = hidden.transpose(0, 1).contiguous()  # (S,B,H)
@@ -722,10 +842,11 @@ class LlamaForCausalLM(nn.Module):
             self.lm_head.weight = self.model.embed_tokens.weight
 
     def forward(self, input_ids, labels=None, pos_offset=0, kv_caches=None,
-                chunk_lens=None):
-        hidden = self.model(input_ids, pos_offset, kv_caches,
-                            **({} if chunk_lens is None
-                               else {"chunk_lens": chunk_lens}))
+                chunk_lens=None, tree=None):
+        kw = {} if chunk_lens is None else {"chunk_lens": chunk_lens}
+        if tree is not None:
+            kw["tree"] = tree
+        hidden = self.model(input_ids, pos_offset, kv_caches, **kw)
         if labels is not None and self.config.loss_chunks > 0:
             from ..utils.chunked_loss import chunked_lm_loss
 

@@ -968,9 +968,10 @@ def _ragged_entry(lib, name):
 
 
 def _decode_attn_check(who, chunk, q, k, v, cos, sin, pos_t, B, Hq, Hkv, Smax,
-                       dev, ragged=False):
+                       dev, ragged=False, tmax=_CA_TMAX):
     """Everything but the cache, for the four fused decode kernels: 2-D
-    q2/k2/v2 (one token) or, with ``chunk``, 3-D q3/k3/v3 (T = 2..8 tokens).
+    q2/k2/v2 (one token) or, with ``chunk``, 3-D q3/k3/v3 (T = 2..8 tokens,
+    2..``tmax`` for the tree kernel).
     Returns T and the strides to launch with.  One token: the (q, kv) row
     strides, the dense widths when B = 1; 2-byte alignment.  A chunk: the
     element strides (q batch, q token, kv batch, kv token), multiples of 8,
@@ -980,9 +981,9 @@ def _decode_attn_check(who, chunk, q, k, v, cos, sin, pos_t, B, Hq, Hkv, Smax,
     if Hkv < 1 or Hq % Hkv or Hq // Hkv not in (1, 2, 4, 8):
         raise ValueError(f"{who}: Hq={Hq}, Hkv={Hkv} outside the kernel "
                          f"contract (GQA rep 1/2/4/8)")
-    if chunk and (q.dim() != 3 or not _CA_TMIN <= q.shape[1] <= _CA_TMAX):
+    if chunk and (q.dim() != 3 or not _CA_TMIN <= q.shape[1] <= tmax):
         raise ValueError(f"{who}: q3 {tuple(q.shape)} must be (B, T, Hq*128) "
-                         f"with {_CA_TMIN} <= T <= {_CA_TMAX}")
+                         f"with {_CA_TMIN} <= T <= {tmax}")
     T = q.shape[1] if chunk else 1
     if Smax < T:
         raise ValueError(f"{who}: a cache of {Smax} rows cannot take {T} "
@@ -1555,6 +1556,95 @@ def chunk_attn_step(q3: torch.Tensor, k3: torch.Tensor, v3: torch.Tensor,
     return _decode_attn_launch(
         fn, True, (q3, k3, v3, kcache, vcache, cos, sin, pos_t),
         B, T, Hq, Hkv, Smax, scale, st)
+
+
+def tree_attn_available() -> bool:
+    lib = _load()
+    return lib is not None and all(
+        hasattr(lib, n) for n in ("tree_attn", "tree_attn_ragged",
+                                  "tree_kv_commit"))
+
+
+_TA_TMAX, _TA_RMAX = 16, 64   # TA_TMAX / TA_RMAX of csrc/tree_attn.hip
+
+
+def tree_attn_step(q3: torch.Tensor, k3: torch.Tensor, v3: torch.Tensor,
+                   kcache: torch.Tensor, vcache: torch.Tensor,
+                   cos: torch.Tensor, sin: torch.Tensor, pos_t: torch.Tensor,
+                   anc: torch.Tensor, depth: torch.Tensor, Hq: int, Hkv: int,
+                   scale: float, *, ragged: bool = False) -> torch.Tensor:
+    """The tree sibling of :func:`chunk_attn_step`: the T = 2..16 new tokens
+    are the nodes of a candidate tree (Medusa), rep * T <= 64.  Tensors as
+    there; ``anc`` and ``depth`` are contiguous int32 (T,) on the device
+    (``utils.medusa_utils.medusa_tree_topology``), shared by the batch.
+
+    Node i is roped at position pos + depth[i], its K/V row is stored at
+    cache row pos + i, and it attends rows [0, pos) and the new rows pos + j
+    with bit j of anc[i] set.  With either kind of position a sequence whose
+    T rows do not all lie in the cache is inactive: no append, zeros out.
+    The kernel clamps depth to [0, T-1] and ignores bits of anc from T up, so
+    a wrong topology gives wrong numbers and no stray access.  No host sync:
+    hipGraph-capturable.  A wrong dtype or shape raises ValueError and
+    launches nothing."""
+    lib = _require_lib()
+    who = "tree_attn_step"
+    if not tree_attn_available():
+        raise RuntimeError("nxd_ops library has no tree_attn — rebuild")
+    B, Smax = _decode_attn_check_cache(who, kcache, vcache, Hkv)
+    T, st = _decode_attn_check(who, True, q3, k3, v3, cos, sin, pos_t, B, Hq,
+                               Hkv, Smax, kcache.device, ragged, _TA_TMAX)
+    if Hq // Hkv * T > _TA_RMAX:
+        raise ValueError(f"{who}: rep * T = {Hq // Hkv * T} query rows per "
+                         f"KV head, the kernel takes {_TA_RMAX}")
+    for name, t in (("anc", anc), ("depth", depth)):
+        if t.dtype != torch.int32 or t.device != kcache.device \
+                or tuple(t.shape) != (T,) or not t.is_contiguous():
+            raise ValueError(f"{who}: {name} must be a contiguous int32 "
+                             f"({T},) tensor on {kcache.device}, got "
+                             f"{t.dtype} {tuple(t.shape)} on {t.device}")
+    fn = lib.tree_attn_ragged if ragged else lib.tree_attn
+    return _decode_attn_launch(
+        fn, True, (q3, k3, v3, kcache, vcache, cos, sin, pos_t, anc, depth),
+        B, T, Hq, Hkv, Smax, scale, st)
+
+
+def tree_kv_commit(kcache: torch.Tensor, vcache: torch.Tensor,
+                   pos_t: torch.Tensor, path: torch.Tensor, *,
+                   ragged: bool = False) -> None:
+    """Pack an accepted root path of a tree step down to consecutive cache
+    rows, in place: for every d >= 1 with ``0 <= path[b, d] < 16``, row
+    pos + d of sequence b takes what row pos + path[b, d] held, K and V of
+    every KV head.  ``path`` int32 (B, L), L <= 16: column 0 is the root
+    (it stays), then the accepted node indices, then -1.  All sources are
+    read before any row is written, so a path like [0, 3, 5, 7] is safe.
+    Entries that are negative, 16 or more, or whose rows fall outside the
+    cache move nothing.  ``pos_t`` as in :func:`tree_attn_step`."""
+    lib = _require_lib()
+    who = "tree_kv_commit"
+    if not tree_attn_available():
+        raise RuntimeError("nxd_ops library has no tree_kv_commit — rebuild")
+    B, Smax = _decode_attn_check_cache(who, kcache, vcache, kcache.shape[1]
+                                       if kcache.dim() == 4 else 0)
+    dev = kcache.device
+    if path.dtype != torch.int32 or path.device != dev or path.dim() != 2 \
+            or path.shape[0] != B or not 1 <= path.shape[1] <= _TA_TMAX \
+            or not path.is_contiguous():
+        raise ValueError(f"{who}: path must be a contiguous int32 ({B}, L) "
+                         f"tensor on {dev} with L <= {_TA_TMAX}, got "
+                         f"{path.dtype} {tuple(path.shape)} on {path.device}")
+    if pos_t.dtype != torch.int64 or pos_t.device != dev \
+            or not pos_t.is_contiguous() \
+            or (tuple(pos_t.shape) != (B,) if ragged else pos_t.numel() != 1):
+        raise ValueError(f"{who}: pos_t must be int64 on {dev}, one element "
+                         f"or with ragged a contiguous ({B},), got "
+                         f"{pos_t.dtype} {tuple(pos_t.shape)} on "
+                         f"{pos_t.device}")
+    rc = lib.tree_kv_commit(_ptr(kcache), _ptr(vcache), _ptr(pos_t),
+                            _ptr(path), B, path.shape[1], kcache.shape[1],
+                            Smax, int(bool(ragged)), _stream())
+    if rc != 0:
+        raise ValueError(f"tree_kv_commit rejected B={B}, "
+                         f"L={path.shape[1]}, Smax={Smax}")
 
 
 def chunk_attn_mx_step(q3: torch.Tensor, k3: torch.Tensor, v3: torch.Tensor,

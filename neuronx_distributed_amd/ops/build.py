@@ -31,7 +31,8 @@ _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {"paged_attn.hip": _NO_PACKED_FP32,
                "paged_attn_mx.hip": _NO_PACKED_FP32,
                "paged_chunk_attn.hip": _NO_PACKED_FP32,
-               "paged_prefill_attn.hip": _NO_PACKED_FP32}
+               "paged_prefill_attn.hip": _NO_PACKED_FP32,
+               "tree_attn.hip": _NO_PACKED_FP32}
 
 
 def _sources():

@@ -55,6 +55,41 @@ def generate_medusa_buffers(medusa_choices: List[List[int]], device=None):
     return out
 
 
+def medusa_tree_topology(medusa_attn_mask: torch.Tensor, device=None):
+    """The ``(anc, depth)`` int32 pair of the tree-attention step
+    (``ops.tree_attn_step``, ``LlamaForCausalLM.forward(tree=...)``) from a
+    (T, T) bool ``medusa_attn_mask`` of :func:`generate_medusa_buffers`:
+    bit j of ``anc[i]`` is mask[i, j], ``depth[i]`` the number of ancestors.
+
+    Validated on the CPU: T <= 16, diagonal and column 0 set, lower
+    triangular (nodes sorted by depth, root first), and every row the union
+    of its parent's row and the node itself."""
+    m = medusa_attn_mask.detach().to("cpu", torch.bool)
+    if m.dim() != 2 or m.shape[0] != m.shape[1] or not 1 <= m.shape[0] <= 16:
+        raise ValueError(f"a (T, T) tree mask with T <= 16, got "
+                         f"{tuple(m.shape)}")
+    T = m.shape[0]
+    if not (m.diagonal().all() and m[:, 0].all()):
+        raise ValueError("every node attends itself and the root: the "
+                         "diagonal and column 0 must be set")
+    if m.triu(1).any():
+        raise ValueError("the tree mask must be lower triangular (root "
+                         "first, nodes sorted by depth)")
+    words = [sum(1 << j for j in range(T) if m[i, j]) for i in range(T)]
+    for i in range(1, T):
+        rest = words[i] & ~(1 << i)
+        parent = rest.bit_length() - 1   # the deepest proper ancestor
+        if rest != words[parent]:
+            raise ValueError(f"row {i} of the tree mask is not its parent's "
+                             f"row ({parent}) plus itself")
+    anc = torch.tensor(words, dtype=torch.int32)
+    depth = torch.tensor([bin(w).count("1") - 1 for w in words],
+                         dtype=torch.int32)
+    if device is not None:
+        anc, depth = anc.to(device), depth.to(device)
+    return anc, depth
+
+
 class MedusaHead(torch.nn.Module):
     """One residual-MLP draft head (reference medusa head design)."""
 
